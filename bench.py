@@ -8,6 +8,12 @@ over ranks (weak scaling: every rank owns `--agents` agents).  Rank 0 prints ONE
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--agents 10000000] [--tasks 10000]
   multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what `value` needs: set-up, warm-up, the K timed steps, the result line.
+--dump-outputs DIR also writes what the last timed step returned (DIR/<name>.npy).  --full adds
+everything else the line can carry: the end-state checks, the election / allocation split, the
+per-kernel and roofline figures, the other SURVEY §8 rows, the CPU baselines and, at N > 1, the
+union-oracle check and the election cost model.
 """
 from __future__ import annotations
 
@@ -25,6 +31,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s)
 REF_PYTHON_RATE = 65_355.0  # agent-rounds/s, SURVEY.md §6 (reference Python, 1 core)
+DUMP_SAMPLE = 500_000  # --dump-outputs: elements kept of a larger array (9 arrays x 4 MB at the most)
 
 
 def parse():
@@ -41,11 +48,18 @@ def parse():
     ap.add_argument("--deg", type=float, default=16.0)
     ap.add_argument("--seed", type=int, default=2026)
     ap.add_argument("--elect-mode", choices=["frontier", "dense"], default="frontier")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every further measurement and check (end-state checks, "
+                         "step split, per-kernel and roofline figures, the other rows, CPU baselines, union-oracle "
+                         "check, cost model); the flags below that select among those act under --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; "
+                         "an array of more than %d elements as a fixed seeded sample of that many)" % DUMP_SAMPLE)
     ap.add_argument("--roofline-rounds", type=int, default=20)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="0 to skip the oracle timing")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: 0 to skip the oracle timing")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--rows", type=int, default=1,
-                    help="0 to skip the other SURVEY §8 rows (C2, C4 auction, physics, protocol, codec)")
+                    help="--full: 0 to skip the other SURVEY §8 rows (C2, C4 auction, physics, protocol, codec)")
     ap.add_argument("--partition", choices=["strips", "blocks"], default="strips",
                     help="N > 1: strips (strip-major IDs: 2 peers per rank, 16-bit columns) or blocks "
                          "(SURVEY §8e's Morton IDs: Morton-ordered blocks, up to 8 peers per rank)")
@@ -91,6 +105,23 @@ def _spin_until_idle():
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """--dump-outputs: every array of `arrays` (what the last timed step returned: device tensors, host
+    arrays, counts) as path/<name><suffix>.npy in float64, which holds every int32 / f32-valued output
+    exactly.  An array of more than DUMP_SAMPLE elements is written as its elements at DUMP_SAMPLE
+    sorted indices drawn from a fixed seed (the same indices in every run of the same shape)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.reshape(-1)
+            if v.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(12345).integers(0, v.numel(), DUMP_SAMPLE))
+                v = v[torch.as_tensor(idx, device=v.device)]
+            v = v.cpu().numpy()
+        np.save(os.path.join(path, name + suffix + ".npy"), np.asarray(v, dtype=np.float64).reshape(-1))
 
 
 def pmc_traffic(kernel_prefix):
@@ -197,6 +228,38 @@ def main():
     # a non-converged election would report max_rounds rounds: refuse to print such a number
     assert r.converged, f"election did not converge in {r.rounds_exec} rounds"
     assert a.stats["mode_used"] in (_lib.ALLOC_BINNED, _lib.ALLOC_DENSE), a.stats
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {
+            "elect_rounds_exec": [r.rounds_exec], "elect_changes": r.changes, "elect_leader": r.leader,
+            "elect_state": r.state, "alloc_winner": a.winner, "alloc_util": a.util, "alloc_won": a.won,
+            "alloc_nclaim": a.nclaim, "alloc_nmsg": a.nmsg})
+    # the result line of a plain run; --full adds the rest below
+    head = {
+        "metric": "agent-rounds/sec (election+allocation) at 10M agents; % of HBM roofline",
+        "value": float(n) * rounds_total / elapsed,
+        "unit": "agent-rounds/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if args.config == "C5" else "weak",
+        "vs_baseline": None,
+        "dtype": "int32+f64",
+        "data": "synthetic (seeded RGG, SplitMix64)",
+        "config": {"workload": "%s: %d agents/GPU, deg %g RGG, election to convergence + %d-task allocation"
+                   % (args.config, n, args.deg, args.tasks),
+                   "agents_per_gpu": n, "edges_per_gpu": e, "tasks": args.tasks,
+                   "elect_mode": args.elect_mode, "alloc_mode": a.stats.get("mode_used"),
+                   "rounds_exec": r.rounds_exec, "parallelism": f"agents sharded x{world}",
+                   "alloc_index": "the cell index of the static positions is built once, outside the timed "
+                                  "steps (alloc_index_build_ms); a step that moves agents rebuilds it"},
+        "build": _lib.provenance(),
+        "alloc_stats": a.stats,
+    }
+    if not args.full:
+        print(json.dumps(head), flush=True)
+        return
     check = final_state_check(sw, r)
 
     agent_rounds = float(n) * rounds_total
@@ -283,25 +346,7 @@ def main():
     if rank == 0:
         value = agent_rounds / elapsed
         out = {
-            "metric": "agent-rounds/sec (election+allocation) at 10M agents; % of HBM roofline",
-            "value": value,
-            "unit": "agent-rounds/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if args.config == "C5" else "weak",
-            "vs_baseline": None,
-            "dtype": "int32+f64",
-            "data": "synthetic (seeded RGG, SplitMix64)",
-            "config": {"workload": "%s: %d agents/GPU, deg %g RGG, election to convergence + %d-task allocation"
-                       % (args.config, n, args.deg, args.tasks),
-                       "agents_per_gpu": n, "edges_per_gpu": e, "tasks": args.tasks,
-                       "elect_mode": args.elect_mode, "alloc_mode": a.stats.get("mode_used"),
-                       "rounds_exec": r.rounds_exec, "parallelism": f"agents sharded x{world}",
-                       "alloc_index": "the cell index of the static positions is built once, outside the timed "
-                                      "steps (alloc_index_build_ms); a step that moves agents rebuilds it"},
+            **dict(head, value=value, ms_per_step=elapsed * 1e3 / args.steps),
             "breakdown_ms": {"elect": t_elect_ms, "alloc": t_alloc_ms},
             "alloc_index_build_ms": float(np.median(idx_ms)),
             # the step's algorithmic bytes (the frontier's per-round counters, DESIGN §4, + the
@@ -709,16 +754,24 @@ def sharded(args, rank, world, dev):
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t[0])
     total_agents = args.agents * world
-    check = sharded_state_check(sh, r)
-    if args.oracle_check:
-        check["union_oracle"] = union_oracle_check(args, sh, r, rank, world)
-    # dominant kernel on every rank: k_sparse_block timed with HIP events over one instrumented
-    # election of this rank's shard graph (owned + ghost rows) -- the kernel the sharded loop
-    # launches every round, on the same graph; rank 0 reports its own, and the spread over ranks
-    dom = shard_roofline(sh, dev)
-    fr = torch.tensor([dom["frac"], -dom["frac"]], dtype=torch.float64, device=cdev)
-    dist.all_reduce(fr, op=dist.ReduceOp.MAX)
-    model = sharded_model(args, sh, rank, world, check) if args.model and getattr(sh, "_native", None) else None
+    if args.dump_outputs:  # every rank writes its own share
+        dump_outputs(args.dump_outputs, {
+            "elect_rounds_exec": [r.rounds_exec], "elect_changes": r.changes, "elect_leader": r.leader,
+            "elect_state": r.state, "alloc_winner": a[0].winner, "alloc_util": a[0].util, "alloc_won": a[1],
+            "alloc_nclaim": a[0].nclaim, "alloc_nmsg": a[0].nmsg}, suffix="_rank%d" % rank)
+    check, dom, fr, model = None, None, None, None
+    if args.full:
+        check = sharded_state_check(sh, r)
+        if args.oracle_check:
+            check["union_oracle"] = union_oracle_check(args, sh, r, rank, world)
+        # dominant kernel on every rank: k_sparse_block timed with HIP events over one instrumented
+        # election of this rank's shard graph (owned + ghost rows) -- the kernel the sharded loop
+        # launches every round, on the same graph; rank 0 reports its own, and the spread over ranks
+        dom = shard_roofline(sh, dev)
+        fr = torch.tensor([dom["frac"], -dom["frac"]], dtype=torch.float64, device=cdev)
+        dist.all_reduce(fr, op=dist.ReduceOp.MAX)
+        if args.model and getattr(sh, "_native", None):
+            model = sharded_model(args, sh, rank, world, check)
     path = _shard_path(sh)
     staged = dist.get_backend() != "nccl"
     if rank == 0:
@@ -779,16 +832,19 @@ def sharded(args, rank, world, dev):
             **({"rccl_double": rccl_double_stats()} if os.environ.get("SWARM_RCCL_PATH") else {}),
             "reference_python": {"value": REF_PYTHON_RATE, "unit": "agent-rounds/s", "cores": 1,
                                  "source": "SURVEY.md §6 (reference election on 1 core of the build container)"},
-            "roofline": dict(dom, frac_max_over_ranks=float(fr[0]), frac_min_over_ranks=-float(fr[1]),
-                             note="rank 0's k_sparse_block over its shard graph (owned + ghost rows), HIP events "
-                                  "on libswarm's stream, one instrumented election of that graph"),
+            "roofline": None,
             "cpu_baseline": None,
         }
-        if args.cpu_baseline:
+        if args.full:
+            out["roofline"] = dict(
+                dom, frac_max_over_ranks=float(fr[0]), frac_min_over_ranks=-float(fr[1]),
+                note="rank 0's k_sparse_block over its shard graph (owned + ghost rows), HIP events "
+                     "on libswarm's stream, one instrumented election of that graph")
+        if args.full and args.cpu_baseline:
             out["cpu_baseline"] = shard_cpu_baseline(sh, tx, ty, tq)
     # C4 on N GPUs beside the headline: 100k agents split over the ranks, 100k tasks replicated,
     # the native sharded auction (the round's bids exchanged by one all-gather per round)
-    if args.rows:
+    if args.full and args.rows:
         c4 = sharded_auction_row(args, rank, world, dev)
         if rank == 0:
             out["rows"] = {"C4_auction_sharded": c4}

@@ -39,7 +39,7 @@ def test_c5_bench_eight_ranks_one_gpu_matches_union_oracle(partition, agents, pi
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "8", "--config", "C5", "--agents", str(agents), "--tasks", "200", "--steps", "1",
-           "--warmup", "0", "--cpu-baseline", "0", "--partition", partition, "--pieces", str(pieces)]
+           "--warmup", "0", "--full", "--cpu-baseline", "0", "--partition", partition, "--pieces", str(pieces)]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     if p.returncode:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)

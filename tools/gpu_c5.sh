@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 P=${PARTITION:-blocks}; N=${NPROC:-8}; TAG=${TAG:-c5}
 SWARM_DIST_BACKEND=gloo timeout -k 10 ${LIMIT:-900} python -u -m torch.distributed.run --nnodes=1 \
     --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $N --config ${CONFIG:-C5} \
-    --partition $P --steps ${STEPS:-2} --warmup 1 --cpu-baseline 0 ${EXTRA:-} \
+    --partition $P --steps ${STEPS:-2} --warmup 1 --full --cpu-baseline 0 ${EXTRA:-} \
     > gpurun_out/${TAG}_$P.json 2> gpurun_out/${TAG}_$P.err
 rc=$?; echo "c5 $P rc=$rc"; tail -c 3000 gpurun_out/${TAG}_$P.json; grep -v "^\[Gloo\]" gpurun_out/${TAG}_$P.err | tail -5
 exit $rc

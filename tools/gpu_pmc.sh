@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 TAG=${TAG:-pmc}
 for ctr in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $ctr --output-format csv -d gpurun_out/pmc_${TAG}_$ctr -o run \
-      -- python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 --roofline-rounds 5 \
+      -- python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 --roofline-rounds 5 \
       > gpurun_out/pmc_${TAG}_$ctr.log 2>&1
   rc=$?; echo "pmc $ctr rc=$rc"
   [ $rc -eq 0 ] || exit $rc

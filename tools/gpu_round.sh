@@ -18,7 +18,7 @@ timeout -k 10 200 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $O/sm
 for ctr in FETCH_SIZE WRITE_SIZE; do
   step pmc $ctr
   timeout -s KILL 300 rocprofv3 --pmc $ctr --output-format csv -d $O/pmc_$ctr -o run \
-      -- python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 --roofline-rounds 5 > $O/pmc_$ctr.log 2>&1 \
+      -- python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 --roofline-rounds 5 > $O/pmc_$ctr.log 2>&1 \
       || { tail $O/pmc_$ctr.log; exit 1; }
 done
 python3 tools/pmc_summary.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE > $O/pmc_traffic.json
@@ -26,8 +26,8 @@ python3 tools/pmc_summary.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE > $O/pmc_traffi
 # tree) at this run's PMC summary, so bench.json cites the same run
 mkdir -p profiles/$TAG && cp $O/pmc_traffic.json profiles/$TAG/ && echo $TAG > profiles/LATEST
 step bench
-timeout -k 10 500 python3 -u bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.log || { tail $O/bench.log; exit 1; }
+timeout -k 10 500 python3 -u bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.log || { tail $O/bench.log; exit 1; }
 step rocprof
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run \
-    -- python3 bench.py --steps 10 --warmup 2 --cpu-baseline 0 --rows 0 > $O/prof.log 2>&1 || { tail $O/prof.log; exit 1; }
+    -- python3 bench.py --full --steps 10 --warmup 2 --cpu-baseline 0 --rows 0 > $O/prof.log 2>&1 || { tail $O/prof.log; exit 1; }
 step done

@@ -40,6 +40,6 @@ for k in sorted(set(fetch) | set(write)):
               "hbm_bytes_per_dispatch": (2.0 * fm + wm) * 1024.0}
 out["_note"] = ("rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE in separate passes; hbm_bytes = (2 x FETCH_SIZE + "
                 "WRITE_SIZE) KB x 1024 (gfx950 FETCH_SIZE counts 64 B per 128-B request); Infinity-Cache hits "
-                "are included in FETCH_SIZE.  Workload: bench.py --steps 1 --warmup 0 (C3, 10M agents).")
+                "are included in FETCH_SIZE.  Workload: bench.py --full --steps 1 --warmup 0 (C3, 10M agents).")
 json.dump(out, sys.stdout, indent=1)
 print()
