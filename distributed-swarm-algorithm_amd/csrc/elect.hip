@@ -15,6 +15,15 @@
 //             per-round change counts, same rounds_exec; each agent's row is read O(changes)
 //             times instead of O(rounds) times.
 //
+// Which neighbours a riser marks (SWARM_MARK_PRUNE, default 1): a riser u of round t with new value m
+// marks itself, and a neighbour w only if the leader it read for w (round t-1's) is below m.  Exact:
+// w changes in round t+1 iff some neighbour u has L_t(u) > L_t(w); such a u rose in round t (had it
+// not, w would have taken its value in round t), and L_{t-1}(w) <= L_t(w) < L_t(u) = m, so u marks
+// w.  The self-mark keeps the double-buffer invariant below: an agent not gathered in round t+1 did
+// not rise in round t.  The argument needs only that values never decrease (ghost overwrites in
+// sharded runs only raise them).  Rows of more than one gather pass, directed graphs, ghost rises
+// and the one-workgroup tail mark every neighbour: a superset, so the forms mix freely.
+//
 // One kernel per round, picked by the host per round from the last change counts it has read
 // (every batch of rounds):
 //   k_elect_dense<MARK=false>  the first dense_rounds-1 rounds (nearly every agent changes)
@@ -526,7 +535,14 @@ __device__ __forceinline__ int wave_excl_scan(int c, int &total) {
 // `first`/`step` select this wave's share; risers mark themselves and their neighbours.  Lane
 // `sub` of an agent takes edges b + sub + G*j (interleaved: one load instruction covers G
 // consecutive edges of every agent it serves, so each touches one cache line per agent).
-template <typename Off, int G, int K, bool DIR, typename CT>
+// PRUNE: a riser with new value m marks a neighbour only if the leader it gathered for it is < m (a
+// neighbour already at m cannot be raised by it; header comment).  No gathered value is above m, so
+// the neighbours to skip are the columns that hold the maximum: each lane keeps them as one bit per
+// column while the values are still live (top) and drops the bits if the group's maximum turns out
+// to be another lane's -- one register across group_max, where the values kept live, or folded into
+// a mask after it, spill.  One-pass rows of symmetric graphs only; the other rows mark every
+// neighbour, a superset.
+template <typename Off, int G, int K, bool DIR, bool PRUNE, typename CT>
 __device__ __forceinline__ void gather_listed(const Off *__restrict__ rp, CT cols,
                                               const Off *__restrict__ hrp, const int32_t *__restrict__ hcol,
                                               const int32_t *__restrict__ P, int32_t *__restrict__ Q,
@@ -557,6 +573,7 @@ __device__ __forceinline__ void gather_listed(const Off *__restrict__ rp, CT col
         }
         int m = own;
         int c[K];
+        unsigned top = 0;  // PRUNE: bit j = column j of the last pass holds the maximum
         for (Off k = b + sub; k < e; k += G * K) {
             if constexpr (std::is_same_v<CT, Col16E>) {
                 bool esc[K];
@@ -580,18 +597,25 @@ __device__ __forceinline__ void gather_listed(const Off *__restrict__ rp, CT col
             for (int j = 0; j < K; ++j) val[j] = ld4(P, Ix(c[j]));
 #pragma unroll
             for (int j = 0; j < K; ++j) m = max(m, val[j]);
+            if constexpr (PRUNE) {  // the columns of this pass that hold the lane's maximum so far
+                top = 0;
+#pragma unroll
+                for (int j = 0; j < K; ++j) top |= unsigned(val[j] == m) << j;
+            }
         }
+        const int ml = m;
         m = group_max<G>(m);
+        if (PRUNE && ml != m) top = 0;  // the group's maximum is another lane's: all of this lane's are below it
         const bool up = valid && m > own;
         if (valid && sub == 0) st4(Q, Ix(v), m);
         if (up) {
             if (sub == 0) aw[stamp_slot(sm, v)] = sw;
             if (DIR) {  // the agents that hear v
                 mark_row<Off>(aw, sm, Col32{hcol}, 0, hrp[v] + sub, hrp[v + 1], Off(G), sw);
-            } else if (e - b <= G * K) {  // one pass: c[] still holds this lane's edges
+            } else if (e - b <= G * K) {  // one pass: c[] still holds this lane's edges (top: those at m)
 #pragma unroll
                 for (int j = 0; j < K; ++j)
-                    if (b + sub + G * j < e) aw[stamp_slot(sm, c[j])] = sw;
+                    if (b + sub + G * j < e && !((top >> j) & 1u)) aw[stamp_slot(sm, c[j])] = sw;
             } else {
                 mark_row<Off>(aw, sm, cols, v & ~63, b + sub, e, Off(G), sw);
             }
@@ -654,7 +678,8 @@ __device__ __forceinline__ void flush_counts(unsigned long long *ring, int t, lo
 
 // One workgroup per chunk of kBlock * S agents: S stamps per thread, the chunk's marked agents
 // compacted in LDS and gathered by the whole workgroup.
-template <typename Off, int S = kScan, bool DIR = false, typename CT = Col32, int G = kG, int K = kKs>
+template <typename Off, int S = kScan, bool DIR = false, typename CT = Col32, int G = kG, int K = kKs,
+          bool PRUNE = false>
 __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_block(
     const Off *__restrict__ rp, CT cols, Frontier f, int t, int guard,
     const Off *__restrict__ hrp = nullptr, const int32_t *__restrict__ hcol = nullptr) {
@@ -743,7 +768,7 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
             listed = listed + total < kListCap ? listed + total : kListCap;
             __syncthreads();  // list entries visible
             if (listed < kListCap) break;  // everything fitted
-            gather_listed<Off, G, K, DIR>(rp, cols, hrp, hcol, P, Q, aw, f.wsm, sw, s_list, listed, wid * (64 / G),
+            gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, f.wsm, sw, s_list, listed, wid * (64 / G),
                                           kBlock / G, f.c_lo, f.n_count, my_chg, my_act, my_edges);
             listed = 0;
             __syncthreads();  // the list is reused
@@ -753,7 +778,7 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
     ph_listed = wall_clock64();
 #endif
     if (listed > 0)
-        gather_listed<Off, G, K, DIR>(rp, cols, hrp, hcol, P, Q, aw, f.wsm, sw, s_list, listed, wid * (64 / G),
+        gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, f.wsm, sw, s_list, listed, wid * (64 / G),
                                       kBlock / G, f.c_lo, f.n_count, my_chg, my_act, my_edges);
 #ifdef SWARM_PHASES
     ph_gathered = wall_clock64() + (my_chg & 0);
@@ -1155,7 +1180,10 @@ struct Tuning {
     int tail_wg = 0;           // > 0: the one-workgroup tail (k_tail_wg) once a round's marks fit this many
     int tail_log = 0;          // SWARM_TAIL_LOG=1: per-round clocks of the tail to stderr (experiment aid)
     int look = 8;              // SWARM_LOOKAHEAD: rounds between a batch's read-back point and its end
+    int mark_prune = 1;        // SWARM_MARK_PRUNE: sparse-round risers mark only the neighbours they can still
+                               // raise (0: every neighbour)
     Tuning() {
+        mark_prune = env_int("SWARM_MARK_PRUNE", 1);
         look = env_int("SWARM_LOOKAHEAD", 8);
         if (look < 1) look = 1;
         if (look > 64) look = 64;
@@ -1311,6 +1339,35 @@ RoundKind plan_round(int t) {
     return RK_SPARSE;
 }
 
+// The sparse round of a symmetric graph: chunk size and column type from the frontier, PRUNE from
+// SWARM_MARK_PRUNE.
+template <typename Off, bool PRUNE>
+int launch_sparse_round(const Off *rp, const int32_t *col, const Frontier &f, int t, int guard, hipStream_t s) {
+    const bool small = f.sm.cshift == 9;  // small swarm: 512-agent chunks, 4x the workgroups
+    const dim3 grid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
+    const Col32 c32{col};
+    if (f.c16 && f.c16_esc && small)
+        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col16E, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
+                           Col16E{f.c16, col}, f, t, guard, nullptr, nullptr);
+    else if (f.c16 && f.c16_esc)
+        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col16E, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
+                           Col16E{f.c16, col}, f, t, guard, nullptr, nullptr);
+    else if (f.c16 && small)
+        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col16, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
+                           Col16{f.c16}, f, t, guard, nullptr, nullptr);
+    else if (f.c16)
+        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col16, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
+                           Col16{f.c16}, f, t, guard, nullptr, nullptr);
+    else if (small)
+        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col32, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp, c32,
+                           f, t, guard, nullptr, nullptr);
+    else
+        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col32, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
+                           c32, f, t, guard, nullptr, nullptr);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
 // hrp/hcol: the transpose CSR of a directed graph (who hears each agent), or NULL (symmetric).
 template <typename Off>
 int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, int t, RoundKind k, int guard,
@@ -1324,31 +1381,20 @@ int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, 
     // parity, it is cleared first, so no stamp outlives the 510 rounds after which its value
     // recurs (take_stamps)
     if (t > 2 && ((t - 1) & 255) < 2) SW_HIP(hipMemsetAsync(f.act[(t + 1) & 1], 0, act_bytes(f.n_all), s));
-    const bool small = f.sm.cshift == 9;  // small swarm: 512-agent chunks, 4x the workgroups
-    const dim3 grid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
-    const Col32 c32{col};
-    if (hrp && small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2, true>), grid, dim3(kBlock), 0, s, rp, c32, f, t, guard, hrp, hcol);
-    else if (hrp)
-        hipLaunchKernelGGL((k_sparse_block<Off, kScan, true>), grid, dim3(kBlock), 0, s, rp, c32, f, t, guard, hrp, hcol);
-    else if (f.c16 && f.c16_esc && small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col16E>), grid, dim3(kBlock), 0, s, rp, Col16E{f.c16, col},
-                           f, t, guard, nullptr, nullptr);
-    else if (f.c16 && f.c16_esc)
-        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col16E>), grid, dim3(kBlock), 0, s, rp,
-                           Col16E{f.c16, col}, f, t, guard, nullptr, nullptr);
-    else if (f.c16 && small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col16>), grid, dim3(kBlock), 0, s, rp, Col16{f.c16}, f, t,
-                           guard, nullptr, nullptr);
-    else if (f.c16)
-        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col16>), grid, dim3(kBlock), 0, s, rp, Col16{f.c16}, f, t,
-                           guard, nullptr, nullptr);
-    else if (small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2>), grid, dim3(kBlock), 0, s, rp, c32, f, t, guard, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((k_sparse_block<Off>), grid, dim3(kBlock), 0, s, rp, c32, f, t, guard, nullptr, nullptr);
-    SW_LAUNCHED();
-    return SWARM_OK;
+    if (hrp) {  // directed: the marks go to hearers, whose leaders the riser did not read -- never pruned
+        const bool small = f.sm.cshift == 9;
+        const dim3 grid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
+        if (small)
+            hipLaunchKernelGGL((k_sparse_block<Off, 2, true>), grid, dim3(kBlock), 0, s, rp, Col32{col}, f, t, guard,
+                               hrp, hcol);
+        else
+            hipLaunchKernelGGL((k_sparse_block<Off, kScan, true>), grid, dim3(kBlock), 0, s, rp, Col32{col}, f, t,
+                               guard, hrp, hcol);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+    return tuning().mark_prune ? launch_sparse_round<Off, true>(rp, col, f, t, guard, s)
+                               : launch_sparse_round<Off, false>(rp, col, f, t, guard, s);
 }
 
 // Algorithmic HBM bytes of one round:

@@ -73,7 +73,8 @@ class ElectResult:
     state: torch.Tensor                 # uint8 [n], storage order (1 FOLLOWER, 3 LEADER)
     converged: bool = True
     rounds_launched: int = 0
-    active_total: int = 0               # agents gathered (dense: all, sparse: marked), summed over rounds
+    active_total: int = 0               # agents gathered (dense: all, sparse: marked -- stamped by a riser under
+                                        # elect.hip's SWARM_MARK_PRUNE rule), summed over rounds
     edges_total: int = 0                # CSR edges visited, summed over rounds
     dense_rounds: int = 0               # rounds run as a full dense sweep
     bytes_total: float = 0.0            # algorithmic HBM bytes of rounds 1..rounds_exec
