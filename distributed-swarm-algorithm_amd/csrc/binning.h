@@ -9,6 +9,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 
 #include "swarm_common.h"
 
@@ -93,6 +94,23 @@ static __global__ __launch_bounds__(kBlock) void k_cell_offsets(const uint32_t *
     }
 }
 
+// Cells of side >= `cell` over g's bounding box (enlarged until the grid has at most max_cells).
+static inline void shape_grid(Grid *g, double cell, int64_t max_cells) {
+    double c = cell > 0 ? cell : 1.0;
+    for (;;) {
+        const double fx = std::floor((g->xmax - g->xmin) / c) + 1.0;
+        const double fy = std::floor((g->ymax - g->ymin) / c) + 1.0;
+        if (fx * fy <= double(max_cells)) {
+            g->ncx = int64_t(fx);
+            g->ncy = int64_t(fy);
+            break;
+        }
+        c *= 1.4142135623730951;
+    }
+    g->cell = c;
+    g->inv_cell = 1.0 / c;
+}
+
 // Bounding box of n positions -> host Grid with cells of side >= `cell` (enlarged if the grid
 // would exceed max_cells).  One host sync (the grid shape sizes the launch).
 static inline int make_grid(swarm_ctx *ctx, int64_t n, const double *pos, double cell, int64_t max_cells,
@@ -115,19 +133,7 @@ static inline int make_grid(swarm_ctx *ctx, int64_t n, const double *pos, double
         return SWARM_ERR_ARG;
     }
     g->xmin = hb[0]; g->ymin = hb[1]; g->xmax = hb[2]; g->ymax = hb[3];
-    double c = cell > 0 ? cell : 1.0;
-    for (;;) {
-        const double fx = std::floor((g->xmax - g->xmin) / c) + 1.0;
-        const double fy = std::floor((g->ymax - g->ymin) / c) + 1.0;
-        if (fx * fy <= double(max_cells)) {
-            g->ncx = int64_t(fx);
-            g->ncy = int64_t(fy);
-            break;
-        }
-        c *= 1.4142135623730951;
-    }
-    g->cell = c;
-    g->inv_cell = 1.0 / c;
+    shape_grid(g, cell, max_cells);
     return SWARM_OK;
 }
 
@@ -159,6 +165,102 @@ static inline int bin_agents(swarm_ctx *ctx, int64_t n, const double *pos, const
     SW_LAUNCHED();
     *sorted_idx = vout;
     *cell_off = off;
+    return SWARM_OK;
+}
+
+// Work a kernel that scans every agent's 3 x 3 cell window will do, from the cell occupancies alone:
+// W = sum over agents of their window's occupancy (a double: a bound, not a count) and the longest
+// serial scan is the largest window (max_win).
+static __global__ __launch_bounds__(kBlock) void k_window_work(const uint32_t *__restrict__ off, Grid g,
+                                                              double *__restrict__ out,
+                                                              unsigned long long *__restrict__ max_win) {
+    double w = 0.0;
+    unsigned long long mx = 0;
+    const int64_t ncells = g.ncx * g.ncy;
+    for (int64_t c = int64_t(blockIdx.x) * kBlock + threadIdx.x; c < ncells; c += int64_t(gridDim.x) * kBlock) {
+        const uint32_t occ = off[c + 1] - off[c];
+        if (occ == 0) continue;
+        const int64_t cx = c % g.ncx, cy = c / g.ncx;
+        const int64_t x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.ncx ? cx + 1 : g.ncx - 1;
+        unsigned long long win = 0;
+        for (int64_t yy = (cy > 0 ? cy - 1 : 0); yy <= cy + 1 && yy < g.ncy; ++yy)
+            win += off[yy * g.ncx + x1 + 1] - off[yy * g.ncx + x0];
+        w += double(occ) * double(win);
+        mx = win > mx ? win : mx;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        w += __shfl_xor(w, o, 64);
+        const unsigned long long m = __shfl_xor(mx, o, 64);
+        mx = m > mx ? m : mx;
+    }
+    // one atomic pair per workgroup: every wave of the grid adding to the same two words serialised
+    // them (0.7 ms at 2M cells)
+    __shared__ double s_w[kBlock / kWave];
+    __shared__ unsigned long long s_mx[kBlock / kWave];
+    if ((threadIdx.x & 63) == 0) {
+        s_w[threadIdx.x >> 6] = w;
+        s_mx[threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kBlock / kWave; ++k) {
+            w += s_w[k];
+            mx = s_mx[k] > mx ? s_mx[k] : mx;
+        }
+        if (w > 0.0) {
+            atomicAdd(out, w);
+            atomicMax(max_win, mx);
+        }
+    }
+}
+
+// Bounds on a window-scanning kernel's work (one thread per agent): a radius graph over co-located
+// agents (a million agents in one cell) would make swarm_build_rgg run for hours on the device.  A
+// deg-16 RGG has windows of ~45 agents: W ~ 45 n (100M agents: 4.5e9), far below these.
+constexpr double kMaxScanPairs = 68719476736.0;          // 2^36 candidate checks in all
+constexpr unsigned long long kMaxWindow = 1ull << 20;    // candidates one thread scans
+
+__host__ __device__ inline bool window_work_exceeded(double pairs, unsigned long long max_window) {
+    return pairs > kMaxScanPairs || max_window > kMaxWindow;
+}
+
+inline void set_window_work_error(const char *what, double pairs, unsigned long long max_window) {
+    set_error("%s: %.3g candidate pairs to scan (limit %.3g), the largest 3x3-cell "
+              "window holds %llu agents (limit %llu) -- co-located agents?",
+              what, pairs, kMaxScanPairs, max_window, kMaxWindow);
+}
+
+// k_window_work of the binned agents, stream-ordered: (*acc)[0] = W (double), (*acc)[1] = max_win (u64).
+static inline int launch_window_work(swarm_ctx *ctx, const uint32_t *off, const Grid &g, hipStream_t s,
+                                     double **acc_out) {
+    double *acc;
+    SW_ALLOC(acc, ctx, S_CELL_END, 64);
+    SW_HIP(hipMemsetAsync(acc, 0, 16, s));
+    hipLaunchKernelGGL(k_window_work, dim3(grid_for(g.ncx * g.ncy, kBlock, 8192)), dim3(kBlock), 0, s, off, g, acc,
+                       reinterpret_cast<unsigned long long *>(acc + 1));
+    SW_LAUNCHED();
+    *acc_out = acc;
+    return SWARM_OK;
+}
+
+// The same, read back and judged on the host (one host sync): SWARM_ERR_RANGE beyond the limits.
+static inline int check_window_work(swarm_ctx *ctx, const uint32_t *off, const Grid &g, hipStream_t s,
+                                    unsigned long long *max_window) {
+    double *acc;
+    const int rc = launch_window_work(ctx, off, g, s, &acc);
+    if (rc) return rc;
+    double *h = static_cast<double *>(pinned(ctx, 64));
+    if (!h) return SWARM_ERR_OOM;
+    SW_HIP(hipMemcpyAsync(h, acc, 16, hipMemcpyDeviceToHost, s));
+    SW_HIP(hipStreamSynchronize(s));
+    unsigned long long m;
+    memcpy(&m, h + 1, 8);
+    *max_window = m;
+    if (window_work_exceeded(h[0], m)) {
+        set_window_work_error("radius graph too dense to build", h[0], m);
+        return SWARM_ERR_RANGE;
+    }
     return SWARM_OK;
 }
 

@@ -56,73 +56,9 @@ __global__ __launch_bounds__(kBlock) void k_rgg_rows(const double2 *__restrict__
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, mine);
 }
 
-// Work the row kernel will do, from the cell occupancies alone: each agent scans the agents of its
-// 3 x 3 cell window, so W = sum over agents of their window's occupancy (a double: a bound, not a
-// count) and the longest serial scan is the largest window (max_win).
-__global__ __launch_bounds__(kBlock) void k_window_work(const uint32_t *__restrict__ off, Grid g,
-                                                       double *__restrict__ out,
-                                                       unsigned long long *__restrict__ max_win) {
-    double w = 0.0;
-    unsigned long long mx = 0;
-    const int64_t ncells = g.ncx * g.ncy;
-    for (int64_t c = int64_t(blockIdx.x) * kBlock + threadIdx.x; c < ncells; c += int64_t(gridDim.x) * kBlock) {
-        const uint32_t occ = off[c + 1] - off[c];
-        if (occ == 0) continue;
-        const int64_t cx = c % g.ncx, cy = c / g.ncx;
-        const int64_t x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.ncx ? cx + 1 : g.ncx - 1;
-        unsigned long long win = 0;
-        for (int64_t yy = (cy > 0 ? cy - 1 : 0); yy <= cy + 1 && yy < g.ncy; ++yy)
-            win += off[yy * g.ncx + x1 + 1] - off[yy * g.ncx + x0];
-        w += double(occ) * double(win);
-        mx = win > mx ? win : mx;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        w += __shfl_xor(w, o, 64);
-        const unsigned long long m = __shfl_xor(mx, o, 64);
-        mx = m > mx ? m : mx;
-    }
-    if ((threadIdx.x & 63) == 0 && w > 0.0) {
-        atomicAdd(out, w);
-        atomicMax(max_win, mx);
-    }
-}
-
-// Bounds on the row kernel's work (one thread per agent): a radius graph over co-located agents
-// (a million agents in one cell) would make swarm_build_rgg run for hours on the device.  A deg-16
-// RGG has windows of ~45 agents: W ~ 45 n (100M agents: 4.5e9), far below these.
-constexpr double kMaxScanPairs = 68719476736.0;          // 2^36 candidate checks in all
-constexpr unsigned long long kMaxWindow = 1ull << 20;    // candidates one thread scans
 constexpr unsigned long long kInKernelSort = 64;         // longer windows: rows sorted by hipCUB
 
 }  // namespace
-}  // namespace swarm
-
-namespace swarm {
-static int check_window_work(swarm_ctx *ctx, const uint32_t *off, const Grid &g, hipStream_t s,
-                             unsigned long long *max_window) {
-    double *acc;
-    SW_ALLOC(acc, ctx, S_CELL_END, 64);
-    SW_HIP(hipMemsetAsync(acc, 0, 16, s));
-    unsigned long long *mx = reinterpret_cast<unsigned long long *>(acc + 1);
-    hipLaunchKernelGGL(k_window_work, dim3(grid_for(g.ncx * g.ncy, kBlock, 8192)), dim3(kBlock), 0, s, off, g, acc,
-                       mx);
-    SW_LAUNCHED();
-    double *h = static_cast<double *>(pinned(ctx, 64));
-    if (!h) return SWARM_ERR_OOM;
-    SW_HIP(hipMemcpyAsync(h, acc, 16, hipMemcpyDeviceToHost, s));
-    SW_HIP(hipStreamSynchronize(s));
-    unsigned long long m;
-    memcpy(&m, h + 1, 8);
-    *max_window = m;
-    if (h[0] > kMaxScanPairs || m > kMaxWindow) {
-        set_error("radius graph too dense to build: %.3g candidate pairs to scan (limit %.3g), the largest 3x3-cell "
-                  "window holds %llu agents (limit %llu) -- co-located agents?",
-                  h[0], kMaxScanPairs, m, kMaxWindow);
-        return SWARM_ERR_RANGE;
-    }
-    return SWARM_OK;
-}
 }  // namespace swarm
 
 extern "C" {

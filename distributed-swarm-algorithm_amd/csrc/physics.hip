@@ -17,9 +17,14 @@
 // the HBM traffic: 16 B per edge + 80 B per agent); obstacles staged in LDS per workgroup.
 // A zero distance to an obstacle centre or a neighbour makes the reference raise
 // ZeroDivisionError; here it yields non-finite values and is counted (n_singular).
+//
+// swarm_physics_run_sensed runs several such steps and senses each step's neighbours from that
+// step's positions (contract S1; the reference's simulator refreshes the neighbour lists before
+// every tick): per step the agents are binned and one fused kernel reads the 3 x 3 cell windows
+// directly -- no degree pass, no scan, no CSR in memory.
 #include <cmath>
 
-#include "swarm_common.h"
+#include "binning.h"
 
 namespace swarm {
 namespace {
@@ -68,6 +73,137 @@ __device__ __forceinline__ double sqrt_core(double x) {  // v_rsq_f64 + Newton s
     return __builtin_fma(d, h, g);
 }
 
+// The pieces of one agent's step as functions.  separation_term is shared by k_physics (neighbours from
+// a CSR) and k_physics_sensed (neighbours from the step's own cell windows): the same code, hence the same
+// bits.  The others restate k_physics' statements for k_physics_sensed (see the note at k_physics).
+
+// Formation (agent.py:96-111): a FOLLOWER with a leader retargets its V slot behind the leader's
+// f32-rounded position.  Returns whether the agent has a target (moves); t = that target.
+__device__ __forceinline__ bool formation_target(int64_t i, const int32_t *__restrict__ ids,
+                                                 const uint8_t *__restrict__ state,
+                                                 const int32_t *__restrict__ leader,
+                                                 const double2 *__restrict__ pin, double2 *__restrict__ tgt,
+                                                 uint8_t *__restrict__ has_t, double2 &t) {
+    t = tgt[i];
+    bool has = has_t[i] != 0;
+    const int32_t L = leader[i];
+    if (state[i] == SWARM_FOLLOWER && L >= 0) {
+        const double2 lp = pin[L];
+        const double lx = double(float(lp.x)), ly = double(float(lp.y));
+        const double rank = double(ids[i]);
+        const double xo = -2.0 * rank;
+        const double yo = (ids[i] % 2 == 0) ? 2.0 * rank : -2.0 * rank;
+        t = make_double2(lx + xo, ly + yo);
+        tgt[i] = t;
+        if (!has) has_t[i] = 1;
+        has = true;
+    }
+    return has;
+}
+
+// Obstacle repulsion (agent.py:128-146), obstacles in list order: every workgroup stages them through
+// LDS (all lanes join the barriers, moving or not).
+__device__ __forceinline__ void obstacle_forces(double *s_obs, int64_t m, const double *__restrict__ obs, bool moving,
+                                                double px, double py, double &frx, double &fry,
+                                                unsigned long long &sing) {
+    for (int64_t o0 = 0; o0 < m; o0 += kObsLds) {
+        const int64_t cnt = (m - o0 < kObsLds) ? m - o0 : kObsLds;
+        __syncthreads();
+        for (int64_t q = threadIdx.x; q < 3 * cnt; q += kBlock) s_obs[q] = obs[3 * o0 + q];
+        __syncthreads();
+        if (moving)
+            for (int64_t o = 0; o < cnt; ++o) {
+                const double ox = s_obs[3 * o], oy = s_obs[3 * o + 1], r = s_obs[3 * o + 2];
+                const double ex = px - ox, ey = py - oy;
+                const double s2 = ex * ex + ey * ey;
+                // far obstacles (most): sqrt(s2) - r >= 5 for certain, so the exact test below could
+                // not apply the force -- skip its square root (the margin 1e-12 is far above the
+                // roundings of s2, the square root and the subtraction; NaN falls through)
+                const double rr = 5.0 + r;
+                if (s2 > rr * rr * (1.0 + 1e-12)) continue;
+                double d = sqrt(s2) - r;
+                if (d <= 0.001) d = 0.001;
+                if (d < 5.0) {
+                    const double mag = 50.0 * (1.0 / d - 1.0 / 5.0) / (d * d);
+                    const double nrm = sqrt(s2);
+                    sing += nrm == 0.0;
+                    frx += (ex / nrm) * mag;
+                    fry += (ey / nrm) * mag;
+                }
+            }
+    }
+}
+
+// One neighbour's separation term (agent.py:149-160) from the offset (ex, ey) to it and
+// s2 = ex * ex + ey * ey: added to the running sums when the neighbour is within the 2.0 personal
+// space.  The sums travel by value: with reference parameters the compiler arranged k_physics' unrolled
+// row loop differently (20 more instructions, 1.4 % slower); this form compiles it as before the lift.
+struct SepAcc {
+    double x, y;              // separation force so far
+    unsigned long long sing;  // zero distances so far
+};
+__device__ __forceinline__ SepAcc separation_term(double ex, double ey, double s2, SepAcc acc) {
+    if (!SWARM_PHYS_LIBM && in_range(ex) && in_range(ey) && in_range(s2)) {
+        // both offsets nonzero and normal: the norm is in [2^-500, 2^251), d * d in
+        // [1e-6, 4), every quotient normal -- the range steps are the identity
+        const double nrm = sqrt_core(s2);
+        if (nrm < 2.0) {
+            const double d = nrm <= 0.001 ? 0.001 : nrm;
+            const double dd = d * d;
+            const double mag = div_by(20.0, dd, rcp_refined(dd));
+            const double rn = rcp_refined(nrm);
+            acc.x += div_by(ex, nrm, rn) * mag;
+            acc.y += div_by(ey, nrm, rn) * mag;
+        }
+        return acc;
+    }
+    double d = sqrt(s2);
+    if (d < 2.0) {
+        if (d <= 0.001) d = 0.001;
+        const double mag = 20.0 / (d * d);
+        const double nrm = sqrt(s2);
+        acc.sing += nrm == 0.0;
+        acc.x += (ex / nrm) * mag;
+        acc.y += (ey / nrm) * mag;
+    }
+    return acc;
+}
+
+// Attraction to the target beyond 0.5 (agent.py:118-125).
+__device__ __forceinline__ void attraction(double px, double py, double2 t, double &fax, double &fay) {
+    const double gx = t.x - px, gy = t.y - py;
+    if (sqrt(gx * gx + gy * gy) > 0.5) {
+        fax = 1.0 * gx;
+        fay = 1.0 * gy;
+    }
+}
+
+// The three forces summed, the speed clamp (agent.py:169-174) and the Euler step (177-178).
+__device__ __forceinline__ void integrate(int64_t i, double px, double py, double fax, double fay, double frx,
+                                          double fry, double fsx, double fsy, double dt, double max_speed,
+                                          double2 *__restrict__ vel, double2 *__restrict__ pout) {
+    const double f0 = fax + frx + fsx, f1 = fay + fry + fsy;
+    const double vmag = sqrt(f0 * f0 + f1 * f1);
+    double2 v;
+    if (vmag > max_speed) {
+        const double scale = max_speed / vmag;
+        v = make_double2(f0 * scale, f1 * scale);
+    } else {
+        v = make_double2(f0, f1);
+    }
+    vel[i] = v;
+    pout[i] = make_double2(px + v.x * dt, py + v.y * dt);
+}
+
+__device__ __forceinline__ void count_singular(unsigned long long sing, unsigned long long *__restrict__ singular) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sing += __shfl_xor(sing, off, 64);
+    if ((threadIdx.x & 63) == 0 && sing) atomicAdd(singular, sing);
+}
+
+// k_physics keeps its body written out and shares only the separation term: routed through the helpers
+// above (formation_target, obstacle_forces, attraction, integrate) the compiler laid its blocks out
+// differently and the f1 step measured 1-2 % slower; in this form its machine code is what it was.
 __global__ __launch_bounds__(kBlock, 8) void k_physics(int64_t n, const int32_t *__restrict__ ids,
                                                    const uint8_t *__restrict__ state,
                                                    const int32_t *__restrict__ leader,
@@ -156,30 +292,10 @@ __global__ __launch_bounds__(kBlock, 8) void k_physics(int64_t n, const int32_t 
             for (int u = 0; u < kNb; ++u) {
                 if (jj[u] < 0) continue;
                 const double ex = px - qq[u].x, ey = py - qq[u].y;
-                const double s2 = ex * ex + ey * ey;
-                if (!SWARM_PHYS_LIBM && in_range(ex) && in_range(ey) && in_range(s2)) {
-                    // both offsets nonzero and normal: the norm is in [2^-500, 2^251), d * d in
-                    // [1e-6, 4), every quotient normal -- the range steps are the identity
-                    const double nrm = sqrt_core(s2);
-                    if (nrm < 2.0) {
-                        const double d = nrm <= 0.001 ? 0.001 : nrm;
-                        const double dd = d * d;
-                        const double mag = div_by(20.0, dd, rcp_refined(dd));
-                        const double rn = rcp_refined(nrm);
-                        fsx += div_by(ex, nrm, rn) * mag;
-                        fsy += div_by(ey, nrm, rn) * mag;
-                    }
-                    continue;
-                }
-                double d = sqrt(s2);
-                if (d < 2.0) {
-                    if (d <= 0.001) d = 0.001;
-                    const double mag = 20.0 / (d * d);
-                    const double nrm = sqrt(s2);
-                    sing += nrm == 0.0;
-                    fsx += (ex / nrm) * mag;
-                    fsy += (ey / nrm) * mag;
-                }
+                const SepAcc r = separation_term(ex, ey, ex * ex + ey * ey, SepAcc{fsx, fsy, sing});
+                fsx = r.x;
+                fsy = r.y;
+                sing = r.sing;
             }
         }
         const double f0 = fax + frx + fsx, f1 = fay + fry + fsy;
@@ -197,6 +313,128 @@ __global__ __launch_bounds__(kBlock, 8) void k_physics(int64_t n, const int32_t 
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sing += __shfl_xor(sing, off, 64);
     if ((threadIdx.x & 63) == 0 && sing) atomicAdd(singular, sing);
+}
+
+
+// ---- sensed step (contract S1): the neighbours of a step are sensed from that step's positions ----
+//
+// k_physics with the CSR replaced by the agent's 3 x 3 cell window of the step's binning (binning.h):
+// agent i senses j != i iff dx * dx + dy * dy <= r2 (swarm_build_rgg's rule) and applies the sensed
+// neighbours in ascending storage index (a swarm_build_rgg row's order).  A window is up to nine runs
+// of sorted_idx, one per cell, each ascending (the sort is stable): a streaming nine-way merge -- nine
+// cursors and nine head indices in registers, the smallest head taken each turn -- visits the
+// candidates in ascending index with no list, no capacity and no fallback.  Threads are mapped in
+// cell-sorted order over a cell-sorted copy of the positions (psort[q] = pin[sorted_idx[q]]), so a
+// wave's lanes walk the same windows and a candidate's position is read at its cursor, next to its
+// index, not gathered.  Cells of side >= min(R, 2) (1 + 1e-9) suffice: a neighbour farther than 2.0
+// adds no term.  A non-finite agent sits in an edge cell (cell_coord), fails every <= and so senses
+// nobody and is sensed by nobody.  st[0] != 0 (a step refused for its window work): the step only
+// copies the positions through.
+constexpr int32_t kNoHead = 0x7fffffff;
+
+__global__ __launch_bounds__(kBlock) void k_sorted_positions(const double2 *__restrict__ pin, int64_t n,
+                                                            const int32_t *__restrict__ sorted_idx,
+                                                            double2 *__restrict__ psort) {
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n; q += int64_t(gridDim.x) * kBlock)
+        psort[q] = pin[sorted_idx[q]];
+}
+
+// st[0]: 0, or 1 + the first step whose window work exceeds swarm_build_rgg's limits (every later step
+// is then a no-op); st[2], st[3]: that step's candidate pairs (a double's bits) and largest window.
+__global__ void k_sense_verdict(const double *__restrict__ acc, unsigned long long *__restrict__ st, int32_t step) {
+    if (st[0] != 0) return;
+    const unsigned long long *u = reinterpret_cast<const unsigned long long *>(acc);
+    if (window_work_exceeded(acc[0], u[1])) {
+        st[2] = u[0];
+        st[3] = u[1];
+        st[0] = 1ull + unsigned(step);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_physics_sensed(
+    int64_t n, const int32_t *__restrict__ ids, const uint8_t *__restrict__ state, const int32_t *__restrict__ leader,
+    const double2 *__restrict__ pin, double2 *__restrict__ pout, double2 *__restrict__ vel, double2 *__restrict__ tgt,
+    uint8_t *__restrict__ has_t, int64_t m, const double *__restrict__ obs, Grid g, double r2,
+    const int32_t *__restrict__ sorted_idx, const uint32_t *__restrict__ off, const double2 *__restrict__ psort,
+    double dt, double max_speed, unsigned long long *__restrict__ st) {
+    __shared__ double s_obs[kObsLds * 3];
+    const bool stopped = st[0] != 0;  // uniform over the grid: written by an earlier kernel of the stream
+    unsigned long long sing = 0;
+    for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
+        const int64_t q0 = base + threadIdx.x;
+        const bool valid = q0 < n;
+        if (stopped) {
+            if (valid) pout[q0] = pin[q0];
+            continue;
+        }
+        int64_t i = 0;
+        double px = 0, py = 0, frx = 0.0, fry = 0.0;
+        bool moving = false;
+        double2 t = make_double2(0, 0);
+        if (valid) {
+            i = sorted_idx[q0];
+            const double2 p = psort[q0];
+            px = p.x;
+            py = p.y;
+            moving = formation_target(i, ids, state, leader, pin, tgt, has_t, t);
+        }
+        obstacle_forces(s_obs, m, obs, moving, px, py, frx, fry, sing);
+        if (!moving) {
+            if (valid) pout[i] = make_double2(px, py);
+            continue;
+        }
+        // the nine cells of the window: cursor, end and head index of each run (an absent cell: empty)
+        const int64_t cx = cell_coord(px, g.xmin, g.inv_cell, g.ncx);
+        const int64_t cy = cell_coord(py, g.ymin, g.inv_cell, g.ncy);
+        uint32_t cur[9], end[9];
+        int32_t head[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int64_t yy = cy + (k / 3) - 1, xx = cx + (k % 3) - 1;
+            const bool in = yy >= 0 && yy < g.ncy && xx >= 0 && xx < g.ncx;
+            const int64_t c = in ? yy * g.ncx + xx : 0;
+            cur[k] = in ? off[c] : 0u;
+            end[k] = in ? off[c + 1] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kNoHead;
+        double fax = 0.0, fay = 0.0;
+        attraction(px, py, t, fax, fay);
+        double fsx = 0.0, fsy = 0.0;
+        for (;;) {
+            int32_t j = head[0];
+#pragma unroll
+            for (int k = 1; k < 9; ++k) j = head[k] < j ? head[k] : j;
+            if (j == kNoHead) break;
+            uint32_t q = 0, e = 0;  // the run that holds j (indices are distinct: exactly one)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const bool hit = head[k] == j;
+                q = hit ? cur[k] : q;
+                e = hit ? end[k] : e;
+            }
+            const double2 o = psort[q];
+            const uint32_t qn = q + 1;
+            const int32_t hn = qn < e ? sorted_idx[qn] : kNoHead;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const bool hit = head[k] == j;
+                cur[k] = hit ? qn : cur[k];
+                head[k] = hit ? hn : head[k];
+            }
+            if (j == int32_t(i)) continue;
+            const double ex = px - o.x, ey = py - o.y;
+            const double s2 = ex * ex + ey * ey;
+            if (s2 <= r2) {
+                const SepAcc r = separation_term(ex, ey, s2, SepAcc{fsx, fsy, sing});
+                fsx = r.x;
+                fsy = r.y;
+                sing = r.sing;
+            }
+        }
+        integrate(i, px, py, fax, fay, frx, fry, fsx, fsy, dt, max_speed, vel, pout);
+    }
+    count_singular(sing, st + 1);
 }
 
 }  // namespace
@@ -234,6 +472,96 @@ int swarm_physics_step(swarm_ctx *ctx, int64_t n, const int32_t *ids, const uint
         SW_HIP(hipMemcpyAsync(h, d_sing, 8, hipMemcpyDeviceToHost, s));
         SW_HIP(hipStreamSynchronize(s));
         *n_singular = int64_t(*h);
+    }
+    return SWARM_OK;
+}
+
+int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, const uint8_t *state,
+                             const int32_t *leader_index, double *pos, double *vel, double *target,
+                             uint8_t *has_target, int64_t m, const double *obstacles, double sense_radius,
+                             int32_t steps, double dt, double max_speed, int32_t *steps_done, int64_t *n_singular,
+                             void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(n >= 0 && n < (int64_t(1) << 31) - 1 && m >= 0, "sizes out of range");
+    SW_ARG(steps >= 0, "steps must not be negative");
+    SW_ARG(sense_radius > 0 && std::isfinite(sense_radius), "sense_radius must be positive and finite");
+    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
+    SW_ARG(n == 0 || (ids && state && leader_index && pos && vel && target && has_target), "NULL agent array");
+    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0 || steps == 0) {
+        if (steps_done) *steps_done = n == 0 ? steps : 0;
+        if (n_singular) *n_singular = 0;
+        return SWARM_OK;
+    }
+    // One grid for the whole call: no agent moves more than |max_speed * dt| a step, so the entry bounding
+    // box grown by the run's reach holds every finite position of every step (cell_coord clamps the rest
+    // to an edge cell, which keeps two agents within R in adjacent cells).  Host wait 1 of 2; non-finite
+    // positions are refused here, before anything is written.
+    const double cell = (sense_radius < 2.0 ? sense_radius : 2.0) * (1.0 + 1e-9);
+    const int64_t cap4 = 4 * n + 1024, max_cells = cap4 < (int64_t(1) << 31) ? cap4 : (int64_t(1) << 31);
+    Grid g;
+    int rc = make_grid(ctx, n, pos, cell, max_cells, &g, s);
+    if (rc) return rc;
+    double reach = double(steps) * std::fabs(max_speed * dt);
+    if (!(reach < 1e12)) reach = 1e12;  // any box is exact; beyond it the agents share the edge cells
+    g.xmin -= reach;
+    g.ymin -= reach;
+    g.xmax += reach;
+    g.ymax += reach;
+    shape_grid(&g, cell, max_cells);
+    double2 *other, *psort;
+    unsigned long long *st;
+    SW_ALLOC(other, ctx, S_SENSE_POS, size_t(n) * 16);
+    SW_ALLOC(psort, ctx, S_SENSE_SORTED, size_t(n) * 16);
+    SW_ALLOC(st, ctx, S_SENSE_STATE, 64);
+    unsigned long long *h = static_cast<unsigned long long *>(pinned(ctx, 64));
+    if (!h) return SWARM_ERR_OOM;
+    SW_HIP(hipMemsetAsync(st, 0, 32, s));
+    const double r2 = sense_radius * sense_radius;
+    double2 *buf[2] = {reinterpret_cast<double2 *>(pos), other};
+    const dim3 grid(grid_for(n, kBlock, 8192));
+    auto queue_step = [&](int32_t k) -> int {
+        const double2 *pin = buf[k & 1];
+        int32_t *sorted;
+        uint32_t *off;
+        double *acc;
+        int rc;
+        if ((rc = bin_agents(ctx, n, reinterpret_cast<const double *>(pin), g, &sorted, &off, s))) return rc;
+        // the step's window work against swarm_build_rgg's limits, judged on the device: a refused step
+        // sets the stop word, and it and every later step only copy the positions through
+        if ((rc = launch_window_work(ctx, off, g, s, &acc))) return rc;
+        hipLaunchKernelGGL(k_sense_verdict, dim3(1), dim3(1), 0, s, acc, st, k);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_sorted_positions, grid, dim3(kBlock), 0, s, pin, n, sorted, psort);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_physics_sensed, grid, dim3(kBlock), 0, s, n, ids, state, leader_index, pin,
+                           buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel), reinterpret_cast<double2 *>(target),
+                           has_target, m, obstacles, g, r2, sorted, off, psort, dt, max_speed, st);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    };
+    // a step that could not be queued (scratch, a launch error) ends the run after the steps before it:
+    // its fused kernel did not run, so the state after `queued` steps is whole, and it is reported as
+    // any other result before the step's error is returned
+    int32_t queued = 0;
+    for (rc = SWARM_OK; queued < steps; ++queued)
+        if ((rc = queue_step(queued))) break;
+    if (queued & 1) SW_HIP(hipMemcpyAsync(pos, other, size_t(n) * 16, hipMemcpyDeviceToDevice, s));
+    SW_HIP(hipMemcpyAsync(h, st, 32, hipMemcpyDeviceToHost, s));
+    SW_HIP(hipStreamSynchronize(s));  // host wait 2 of 2
+    const int32_t done = h[0] ? int32_t(h[0] - 1) : queued;
+    if (steps_done) *steps_done = done;
+    if (n_singular) *n_singular = int64_t(h[1]);
+    if (rc) return rc;
+    if (h[0]) {
+        double pairs;
+        memcpy(&pairs, h + 2, 8);
+        char what[96];
+        snprintf(what, sizeof(what), "agents too dense to sense at step %d (%d steps done)", int(done), int(done));
+        set_window_work_error(what, pairs, h[3]);
+        return SWARM_ERR_RANGE;
     }
     return SWARM_OK;
 }

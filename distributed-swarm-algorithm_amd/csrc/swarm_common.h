@@ -57,6 +57,9 @@ enum Slot {
     S_ENC_FLAGS,      // codec: tile ticket + per-tile look-back words (kept across calls, tagged by epoch)
     S_CHECK,          // election: the 16-bit column check's verdict word
     S_FSM_FLAGS,      // protocol: per-agent records of a run (flag word + timer tick; leader + leader position)
+    S_SENSE_POS,      // sensed physics: the second position buffer of the run's double buffering
+    S_SENSE_SORTED,   // sensed physics: the step's positions in cell-sorted order
+    S_SENSE_STATE,    // sensed physics: stop word, singular count and the refused step's window figures
     S_NUM
 };
 

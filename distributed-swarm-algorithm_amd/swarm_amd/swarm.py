@@ -552,11 +552,19 @@ class Swarm:
         return torch.where(self.state == _lib.FOLLOWER, cand, out).contiguous()
 
     def physics_step(self, obstacles=None, *, sensors=None, leader_index=None, dt: float = 0.1,
-                     max_speed: float = 5.0, steps: int = 1) -> dict:
+                     max_speed: float = 5.0, steps: int = 1, sense_radius: float | None = None) -> dict:
         """`steps` synchronous _update_physics steps (agent.py:94-181) of every agent, in place on
         self.pos (contract P1; swarm_physics_step).  obstacles: (m, 3) [x, y, r]; sensors:
         (row_ptr, col) over storage indices (default: the neighbour graph); leader_index:
-        default self.leader_index().  Velocity / target state lives on the Swarm."""
+        default self.leader_index().  Velocity / target state lives on the Swarm.
+        sense_radius: every step senses its neighbours from that step's positions instead (contract
+        S1; swarm_physics_run_sensed, all steps in one call): the result of build_graph(sense_radius)
+        + physics_step(steps=1) repeated, bit for bit, with no graph built and self.row_ptr /
+        self.col untouched.  `sensors` must then be None.  The dict gains "steps_done"; a step whose
+        cell windows are too dense raises SwarmError (ERR_RANGE) with the steps run before it in
+        self.last_steps_done."""
+        if sense_radius is not None and sensors is not None:
+            raise ValueError("sense_radius senses the neighbours itself: sensors must be None")
         dev, n = self.device, self.n
         if not hasattr(self, "vel"):
             self.vel = torch.zeros((n, 2), dtype=torch.float64, device=dev)
@@ -564,6 +572,20 @@ class Swarm:
             self.has_target = torch.zeros(n, dtype=torch.uint8, device=dev)
         obs = torch.zeros((0, 3), dtype=torch.float64, device=dev) if obstacles is None else \
             _to(obstacles, torch.float64, dev).reshape(-1, 3).contiguous()
+        if sense_radius is not None:
+            li = self.leader_index() if leader_index is None else _to(leader_index, torch.int32, dev)
+            sing, done = ctypes.c_int64(0), ctypes.c_int32(0)
+            p = lambda t: _lib.ptr(t) if n else None  # noqa: E731
+            with torch.cuda.device(dev):
+                rc = _lib.lib().swarm_physics_run_sensed(
+                    _lib.ctx(), n, p(self.ids), p(self.state), p(li), p(self.pos), p(self.vel), p(self.target),
+                    p(self.has_target), obs.shape[0], _lib.ptr(obs) if obs.numel() else None, float(sense_radius),
+                    int(steps), float(dt), float(max_speed), ctypes.byref(done), ctypes.byref(sing), _lib.stream())
+            self.last_steps_done = done.value
+            if done.value:
+                self._cindex = None  # agents moved: the storage order is no longer their cell order
+            _lib.check(rc)
+            return {"singular": sing.value, "steps_done": done.value}
         rp, col = sensors if sensors is not None else (self.row_ptr, self.col)
         if rp is None:
             raise RuntimeError("no sensor graph: pass sensors=(row_ptr, col) or build_graph()")

@@ -468,6 +468,32 @@ int swarm_physics_step(swarm_ctx *ctx, int64_t n, const int32_t *ids, const uint
                        int64_t *n_singular, void *stream);
 
 /*
+ * `steps` physics steps whose neighbours are sensed from the moving positions (contract S1): the
+ * reference's simulator refreshes every agent's neighbour list (update_sensors) before each tick, so
+ * separation (agent.py:148-160) acts on where the neighbours are, not where they were.  Per step, with
+ * P the positions at its start: agent i senses j != i iff dx*dx + dy*dy <= sense_radius^2 (fp64, the
+ * products rounded separately: swarm_build_rgg's rule) and applies the sensed neighbours in ascending
+ * storage index; everything else is swarm_physics_step.  The state after s steps is bit-identical to s
+ * repetitions of swarm_build_rgg(P, sense_radius) + swarm_physics_step on that graph, without a graph
+ * in memory.  pos (n x 2 f64) is in/out and holds the result for any step count (the second buffer is
+ * the ctx's).  steps_done / n_singular (host, may be NULL): steps run; zero distances over all steps.
+ * SWARM_ERR_ARG (nothing written): steps < 0, sense_radius not positive and finite, non-finite dt /
+ * max_speed, non-finite positions at entry.  SWARM_ERR_RANGE: at the start of step *steps_done the
+ * agents' 3 x 3 cell windows exceeded swarm_build_rgg's work limits (2^36 candidate pairs, 2^20 in one
+ * window); pos holds the state after *steps_done steps and no window was scanned for that step or a
+ * later one.  A singular step leaves non-finite positions; such an agent senses nobody and is sensed
+ * by nobody in later steps.  Two host waits per call (the entry bounding box, the final verdict).
+ * n == 0: nothing to do, *steps_done = steps; steps == 0: *steps_done = 0 and the arrays are neither
+ * read nor checked.  Any other error (SWARM_ERR_HIP, SWARM_ERR_OOM) at step k > 0 ends the run there:
+ * *steps_done = k (or the refused step, if earlier), pos holds the state after those steps.
+ */
+int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, const uint8_t *state,
+                             const int32_t *leader_index, double *pos, double *vel, double *target,
+                             uint8_t *has_target, int64_t m, const double *obstacles,
+                             double sense_radius, int32_t steps, double dt, double max_speed,
+                             int32_t *steps_done, int64_t *n_singular, void *stream);
+
+/*
  * Batched wire codec: the reference's transport framing, agent.py:184-214,
  * for m messages at once.  Big-endian '!BBI' header (type, sender, tick) + payload by type:
  * 1 HEARTBEAT '!ff' (a, b = leader x, y), 2 ELECTION_ACCLAIM '!B' (the sender ID), 3 COORDINATOR
