@@ -1,0 +1,53 @@
+// The per-agent records of a protocol run (protocol.hip packs the C-ABI's separate arrays into them at the
+// start of a run and unpacks them at its end), shared with the coupled loop's physics step (physics.hip
+// k_physics_loop), which reads an agent's state, alive flag and last-heard leader position from them.
+#pragma once
+
+#include "swarm_common.h"
+
+namespace swarm {
+
+// An agent's per-tick fields for the run, in one 8-byte record: a receiver touches one line for them
+// instead of four, and the sweep streams 8 B per agent instead of 15.
+//   x: the flag word -- byte 0 state, byte 1 alive, byte 2 bits (kHL: has_leader_pos, kH64, kDirty),
+//      byte 3 tick phase = tick_off mod 10 in [0, 9] ((t + tick_off) % 10 == 0 iff (t + phase) % 10 == 0
+//      for every tick t >= 0);
+//   y: the agent's timer as a tick of the run (relative to t0), exact because the reference's clock is
+//      t * dt: FOLLOWER -- the tick its last_heartbeat_time was set at (last_hb == double(t0 + y) * dt,
+//      the timeout test evaluated on that value, as _check_election_timeout does, agent.py:223);
+//      ELECTION_WAIT -- the first tick t at which now - election_wait_start > election_delay holds
+//      (agent.py:234; found once, when the wait starts: the test is monotone in t for dt > 0), 0 = never.
+//   kH64: the timer is in the caller's f64 arrays instead (a value no tick of the run represents, or
+//      dt <= 0): the test reads them, as before.  kDirty: last_hb changed in the run; the unpack writes
+//      double(t0 + y) * dt (a FOLLOWER entering ELECTION_WAIT writes it at once).
+// Leader and leader position are write-only during a protocol run: one 16-byte record per agent (LRec), one
+// line per heartbeat receiver instead of two.  (The coupled loop's physics step reads the position.)
+constexpr uint32_t kHL = 1, kH64 = 2, kDirty = 4;
+__host__ __device__ __forceinline__ uint8_t fw_state(uint32_t w) { return uint8_t(w); }
+__host__ __device__ __forceinline__ uint8_t fw_alive(uint32_t w) { return uint8_t(w >> 8); }
+__host__ __device__ __forceinline__ uint32_t fw_bits(uint32_t w) { return (w >> 16) & 0xFFu; }
+__host__ __device__ __forceinline__ int32_t fw_phase(uint32_t w) { return int32_t(w >> 24); }
+__host__ __device__ __forceinline__ uint32_t fw_make(uint8_t st, uint8_t al, uint32_t bits, int32_t ph) {
+    return uint32_t(st) | (uint32_t(al) << 8) | (bits << 16) | (uint32_t(ph) << 24);
+}
+
+struct alignas(16) LRec {
+    float x, y;      // leader_pos
+    int32_t leader;  // leader
+    int32_t pad;
+};
+
+// The records of n agents in one scratch buffer: the 8-byte records first, the LRecs after them at the
+// next 16-byte boundary (n * 8 is only 8-byte aligned for odd n).
+inline size_t lrec_offset(int64_t n) { return (size_t(n) * 8 + 15) & ~size_t(15); }
+inline size_t fsm_records_bytes(int64_t n) { return lrec_offset(n) + size_t(n) * 16; }
+
+// One physics step of the coupled update loop (contract U1; physics.hip): every alive agent steps from the
+// snapshot pos_in to pos_out with its own record's state and last-heard leader position; dead agents'
+// positions are copied through.  Queued on `s`; zero distances are added to *singular (device).
+int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, const double *pos_in,
+                        double *pos_out, double *vel, double *target, uint8_t *has_target, int64_t m,
+                        const double *obstacles, const int32_t *row_ptr, const int32_t *col, double dt,
+                        double max_speed, unsigned long long *singular, hipStream_t s);
+
+}  // namespace swarm

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "binning.h"
+#include "fsm_records.h"
 
 namespace swarm {
 namespace {
@@ -315,6 +316,87 @@ __global__ __launch_bounds__(kBlock, 8) void k_physics(int64_t n, const int32_t 
     if ((threadIdx.x & 63) == 0 && sing) atomicAdd(singular, sing);
 }
 
+// ---- the coupled update loop's step (contract U1): _update_physics with the agent's own FSM state ----
+//
+// k_physics for a tick of swarm_update_loop, run after the tick's FSM kernel on the run's records
+// (fsm_records.h) instead of state / leader_index arrays: an alive FOLLOWER whose record has kHL targets the
+// V slot behind its OWN last-heard leader position (LRec: the '!ff' payload as the heartbeat delivered it,
+// up to ten ticks old, from whichever neighbour it accepted last) -- no gather of a leader's row; any other
+// alive agent (ELECTION_WAIT, a new LEADER, a FOLLOWER that has not heard a position) keeps the target it
+// had.  A dead agent's position is copied through and nothing else of it is written.  The forces are the
+// helpers' above in k_physics' order, the neighbour row walked as k_physics walks it: the same bits.
+
+// Formation for agent i from its records.  Returns whether the agent moves; t = its target.
+__device__ __forceinline__ bool formation_target_loop(int64_t i, const int32_t *__restrict__ ids, uint32_t fw,
+                                                      const LRec *__restrict__ lrec, double2 *__restrict__ tgt,
+                                                      uint8_t *__restrict__ has_t, double2 &t) {
+    if (!fw_alive(fw)) return false;
+    t = tgt[i];
+    bool has = has_t[i] != 0;
+    if (fw_state(fw) == SWARM_FOLLOWER && (fw_bits(fw) & kHL)) {
+        const float2 lp = *reinterpret_cast<const float2 *>(&lrec[i].x);
+        const double lx = double(lp.x), ly = double(lp.y);
+        const double rank = double(ids[i]);
+        const double xo = -2.0 * rank;
+        const double yo = (ids[i] % 2 == 0) ? 2.0 * rank : -2.0 * rank;
+        t = make_double2(lx + xo, ly + yo);
+        tgt[i] = t;
+        if (!has) has_t[i] = 1;
+        has = true;
+    }
+    return has;
+}
+
+__global__ __launch_bounds__(kBlock, 8) void k_physics_loop(
+    int64_t n, const int32_t *__restrict__ ids, const uint2 *__restrict__ rec, const LRec *__restrict__ lrec,
+    const double2 *__restrict__ pin, double2 *__restrict__ pout, double2 *__restrict__ vel,
+    double2 *__restrict__ tgt, uint8_t *__restrict__ has_t, int64_t m, const double *__restrict__ obs,
+    const int32_t *__restrict__ rp, const int32_t *__restrict__ col, double dt, double max_speed,
+    unsigned long long *__restrict__ singular) {
+    __shared__ double s_obs[kObsLds * 3];
+    unsigned long long sing = 0;
+    for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
+        const int64_t i = base + threadIdx.x;
+        const bool valid = i < n;
+        double px = 0, py = 0, frx = 0.0, fry = 0.0;
+        bool moving = false;
+        double2 t = make_double2(0, 0);
+        if (valid) {
+            const double2 p = pin[i];
+            px = p.x;
+            py = p.y;
+            moving = formation_target_loop(i, ids, rec[i].x, lrec, tgt, has_t, t);
+        }
+        obstacle_forces(s_obs, m, obs, moving, px, py, frx, fry, sing);
+        if (!moving) {  // dead or without a target: its position in the output buffer too
+            if (valid) pout[i] = make_double2(px, py);
+            continue;
+        }
+        double fax = 0.0, fay = 0.0;
+        attraction(px, py, t, fax, fay);
+        double fsx = 0.0, fsy = 0.0;
+        // the row in chunks of kNb, as k_physics: column loads, position gathers in flight, terms in CSR order
+        for (int32_t k0 = rp[i], e = rp[i + 1]; k0 < e; k0 += kNb) {
+            int32_t jj[kNb];
+#pragma unroll
+            for (int u = 0; u < kNb; ++u) jj[u] = k0 + u < e ? col[k0 + u] : -1;
+            double2 qq[kNb];
+#pragma unroll
+            for (int u = 0; u < kNb; ++u) qq[u] = jj[u] >= 0 ? pin[jj[u]] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int u = 0; u < kNb; ++u) {
+                if (jj[u] < 0) continue;
+                const double ex = px - qq[u].x, ey = py - qq[u].y;
+                const SepAcc r = separation_term(ex, ey, ex * ex + ey * ey, SepAcc{fsx, fsy, sing});
+                fsx = r.x;
+                fsy = r.y;
+                sing = r.sing;
+            }
+        }
+        integrate(i, px, py, fax, fay, frx, fry, fsx, fsy, dt, max_speed, vel, pout);
+    }
+    count_singular(sing, singular);
+}
 
 // ---- sensed step (contract S1): the neighbours of a step are sensed from that step's positions ----
 //
@@ -438,6 +520,19 @@ __global__ __launch_bounds__(kBlock) void k_physics_sensed(
 }
 
 }  // namespace
+
+int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, const double *pos_in,
+                        double *pos_out, double *vel, double *target, uint8_t *has_target, int64_t m,
+                        const double *obstacles, const int32_t *row_ptr, const int32_t *col, double dt,
+                        double max_speed, unsigned long long *singular, hipStream_t s) {
+    hipLaunchKernelGGL(k_physics_loop, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids, rec, lrec,
+                       reinterpret_cast<const double2 *>(pos_in), reinterpret_cast<double2 *>(pos_out),
+                       reinterpret_cast<double2 *>(vel), reinterpret_cast<double2 *>(target), has_target, m,
+                       obstacles, row_ptr, col, dt, max_speed, singular);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
 }  // namespace swarm
 
 extern "C" {

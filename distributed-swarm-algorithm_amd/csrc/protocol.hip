@@ -35,9 +35,14 @@
 // launch in which every agent walks its row -- the cross-check.  Both are latency-bound gathers, no
 // arithmetic worth the name.
 // Agents killed at a kill tick (every alive LEADER then) stop receiving and sending.
+//
+// swarm_update_loop (contract U1, agent.py:67-81) runs the same ticks, each followed by the physics step
+// of that tick (physics.hip k_physics_loop, on the run's records): the host loop below is shared
+// (run_ticks), the tick kernels are the same and read the heartbeat positions from the lagged one of the
+// loop's two position buffers.
 #include <cmath>
 
-#include "swarm_common.h"
+#include "fsm_records.h"
 
 namespace swarm {
 namespace {
@@ -61,37 +66,7 @@ __device__ __forceinline__ double jitter_u(uint64_t seed, int32_t id, int64_t t)
     return double(x >> 11) * (1.0 / 9007199254740992.0);
 }
 
-// An agent's per-tick fields for the run, in one 8-byte record (the C-ABI's separate arrays are packed at
-// the start of a run and unpacked at its end): a receiver touches one line for them instead of four, and
-// the sweep streams 8 B per agent instead of 15.
-//   x: the flag word -- byte 0 state, byte 1 alive, byte 2 bits (kHL: has_leader_pos, kH64, kDirty),
-//      byte 3 tick phase = tick_off mod 10 in [0, 9] ((t + tick_off) % 10 == 0 iff (t + phase) % 10 == 0
-//      for every tick t >= 0);
-//   y: the agent's timer as a tick of the run (relative to t0), exact because the reference's clock is
-//      t * dt: FOLLOWER -- the tick its last_heartbeat_time was set at (last_hb == double(t0 + y) * dt,
-//      the timeout test evaluated on that value, as _check_election_timeout does, agent.py:223);
-//      ELECTION_WAIT -- the first tick t at which now - election_wait_start > election_delay holds
-//      (agent.py:234; found once, when the wait starts: the test is monotone in t for dt > 0), 0 = never.
-//   kH64: the timer is in the caller's f64 arrays instead (a value no tick of the run represents, or
-//      dt <= 0): the test reads them, as before.  kDirty: last_hb changed in the run; the unpack writes
-//      double(t0 + y) * dt (a FOLLOWER entering ELECTION_WAIT writes it at once).
-// Leader and leader position are write-only during a run: one 16-byte record per agent (LRec), one line
-// per heartbeat receiver instead of two.
-constexpr uint32_t kHL = 1, kH64 = 2, kDirty = 4;
-__host__ __device__ __forceinline__ uint8_t fw_state(uint32_t w) { return uint8_t(w); }
-__host__ __device__ __forceinline__ uint8_t fw_alive(uint32_t w) { return uint8_t(w >> 8); }
-__host__ __device__ __forceinline__ uint32_t fw_bits(uint32_t w) { return (w >> 16) & 0xFFu; }
-__host__ __device__ __forceinline__ int32_t fw_phase(uint32_t w) { return int32_t(w >> 24); }
-__host__ __device__ __forceinline__ uint32_t fw_make(uint8_t st, uint8_t al, uint32_t bits, int32_t ph) {
-    return uint32_t(st) | (uint32_t(al) << 8) | (bits << 16) | (uint32_t(ph) << 24);
-}
-
-struct alignas(16) LRec {
-    float x, y;      // leader_pos
-    int32_t leader;  // leader
-    int32_t pad;
-};
-
+// The run's per-agent records (uint2 flag word + timer tick, LRec leader + leader position): fsm_records.h.
 struct Fsm {
     uint2 *rec;  // (flag word, timer tick)
     LRec *lrec;
@@ -820,26 +795,39 @@ __global__ void k_sum_traffic(const unsigned long long *__restrict__ tr, unsigne
     }
 }
 
-}  // namespace
-}  // namespace swarm
+// ---------------------------------------------------------------- coupled update loop (contract U1)
+// The physics half of swarm_update_loop: the positions double-buffered over the caller's two arrays (cur =
+// P_{t-1}, lag = P_{t-2} at the start of tick t; the tick's heartbeats read lag, its physics step reads cur
+// and writes lag, then the roles swap), the rest k_physics_loop's arguments.
+struct LoopArgs {
+    double *pos, *pos_prev;
+    double *vel, *target;
+    uint8_t *has_target;
+    int64_t m;
+    const double *obstacles;
+    const int32_t *sense_rp, *sense_col;
+    double max_speed;
+    double *trace;  // frames x n x 2, or NULL
+    int32_t trace_every;
+    int64_t *n_singular;  // host, may be NULL
+};
 
-extern "C" {
-
-int swarm_protocol_run(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
-                       const int32_t *col, const int32_t *hear_row_ptr, const int32_t *hear_col,
-                       const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
-                       double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
-                       int32_t n_kill, int64_t *counts, void *stream) {
-    return swarm_protocol_run_ex(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
-                                 timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, stream);
+// a <-> b, element-wise (an odd number of ticks leaves the newest positions in the caller's pos_prev)
+__global__ __launch_bounds__(kBlock) void k_swap_positions(int64_t n, double2 *__restrict__ a, double2 *__restrict__ b) {
+    for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock) {
+        const double2 p = a[i], q = b[i];
+        a[i] = q;
+        b[i] = p;
+    }
 }
 
-int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
-                          const int32_t *col, const int32_t *hear_row_ptr, const int32_t *hear_col,
-                          const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
-                          double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
-                          int32_t n_kill, double pull_frac, int64_t *counts, int64_t *traffic, void *stream) {
-    using namespace swarm;
+// The ticks t0+1 .. t0+ticks of swarm_protocol_run_ex, and of swarm_update_loop when `loop` is given (each
+// tick then followed by its physics step; `pos` is not used, the heartbeats read the lagged buffer).
+int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
+              const int32_t *col, const int32_t *hear_row_ptr, const int32_t *hear_col, const int32_t *tick_off,
+              const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt, double timeout, double jitter,
+              uint64_t seed, const int64_t *kill_ticks, int32_t n_kill, double pull_frac, int64_t *counts,
+              int64_t *traffic, const LoopArgs *loop, void *stream) {
     SW_ARG(ctx != nullptr && fsm != nullptr, "NULL argument");
     SW_ARG(n >= 0 && n < (int64_t(1) << 31) && ticks >= 0 && t0 >= 0 && n_kill >= 0, "sizes out of range");
     SW_ARG(n_kill == 0 || kill_ticks != nullptr, "kill_ticks is NULL");
@@ -859,16 +847,19 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
     unsigned long long *d_cnt;  // per tick: kShards x 4 partial counters, then the 4 sums
     const size_t part_bytes = size_t(ticks) * kShards * 4 * 8;
     const size_t tr_bytes = size_t(kShards) * kTraffic * 8;
-    SW_ALLOC(d_cnt, ctx, S_TMP0, part_bytes + size_t(ticks) * 4 * 8 + tr_bytes + kTraffic * 8);
+    SW_ALLOC(d_cnt, ctx, S_TMP0, part_bytes + size_t(ticks) * 4 * 8 + tr_bytes + kTraffic * 8 + 64);
     SW_HIP(hipMemsetAsync(d_cnt, 0, part_bytes, s));
     unsigned long long *d_sum = d_cnt + size_t(ticks) * kShards * 4;
     unsigned long long *d_tr = traffic ? d_sum + size_t(ticks) * 4 : nullptr;
     if (d_tr) SW_HIP(hipMemsetAsync(d_tr, 0, tr_bytes, s));
+    // the loop's singular count: the last 64 bytes of the buffer
+    unsigned long long *d_sing = d_sum + size_t(ticks) * 4 + size_t(kShards) * kTraffic + kTraffic;
+    if (loop) SW_HIP(hipMemsetAsync(d_sing, 0, 8, s));
     // the run's records (flag word + timer tick, leader + leader position; unpacked into the caller's arrays
-    // at the end of the run)
+    // at the end of the run), the LRecs on a 16-byte boundary
     uint8_t *recs;
-    SW_ALLOC(recs, ctx, S_FSM_FLAGS, size_t(n) * 24);
-    const Fsm f{reinterpret_cast<uint2 *>(recs), reinterpret_cast<LRec *>(recs + size_t(n) * 8), fsm->last_hb,
+    SW_ALLOC(recs, ctx, S_FSM_FLAGS, size_t(n) * 24 + 16);
+    const Fsm f{reinterpret_cast<uint2 *>(recs), reinterpret_cast<LRec *>(recs + lrec_offset(n)), fsm->last_hb,
                 fsm->wait_start, fsm->delay, t0, t0 + ticks, dt};
     // the sweep role's grid: 2 560 workgroups at most, with half as many in the receive role (10M
     // agents, one-launch ticks, two boxes: 0.1208-0.1212 ms per tick against 0.1232-0.1234 for
@@ -965,7 +956,9 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
     }
     SW_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tick_clk), &clk_buf, sizeof(clk_buf), 0, hipMemcpyHostToDevice, s));
 #endif
+    double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
     for (int64_t t = t0 + 1; t <= t0 + ticks; ++t) {
+        if (loop) pos = lag;  // a heartbeat sent during tick t-1 carries its sender's position of then
         bool kill = false;
         for (int32_t k = 0; k < n_kill; ++k) kill |= kill_ticks[k] == t;
         if (kill) {
@@ -996,6 +989,22 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
                                timeout, jitter, seed, cnt);
         }
         SW_LAUNCHED();
+        if (loop) {  // the tick's physics: P_{t-1} -> P_t over the lagged buffer, then the roles swap
+            const int rc = launch_physics_loop(n, ids, f.rec, f.lrec, cur, lag, loop->vel, loop->target,
+                                               loop->has_target, loop->m, loop->obstacles, loop->sense_rp,
+                                               loop->sense_col, dt, loop->max_speed, d_sing, s);
+            if (rc) return rc;
+            std::swap(cur, lag);
+            const int64_t k = t - t0;
+            if (loop->trace_every > 0 && k % loop->trace_every == 0)
+                SW_HIP(hipMemcpyAsync(loop->trace + size_t(k / loop->trace_every - 1) * size_t(n) * 2, cur,
+                                      size_t(n) * 16, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (loop && cur != loop->pos) {  // an odd number of ticks: pos <- P_end, pos_prev <- P_{end-1}
+        hipLaunchKernelGGL(k_swap_positions, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n,
+                           reinterpret_cast<double2 *>(loop->pos), reinterpret_cast<double2 *>(loop->pos_prev));
+        SW_LAUNCHED();
     }
 #if SWARM_TICK_CLOCKS
     if (clk_buf) {  // experiment aid: header (ticks, workgroups, receive-role workgroups) + the records
@@ -1023,14 +1032,72 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
         SW_HIP(hipStreamSynchronize(s));
         for (int q = 0; q < kTraffic; ++q) traffic[q] = int64_t(hs[q]);
     }
+    unsigned long long *h_sing = nullptr;
+    if (loop && loop->n_singular) {  // read back with the counts: the run's one host wait
+        h_sing = static_cast<unsigned long long *>(pinned(ctx, 64));
+        if (!h_sing) return SWARM_ERR_OOM;
+        SW_HIP(hipMemcpyAsync(h_sing, d_sing, 8, hipMemcpyDeviceToHost, s));
+    }
     if (counts) {
         hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
                            int64_t(ticks), d_cnt, d_sum);
         SW_LAUNCHED();
         SW_HIP(hipMemcpyAsync(counts, d_sum, size_t(ticks) * 4 * 8, hipMemcpyDeviceToHost, s));
-        SW_HIP(hipStreamSynchronize(s));
     }
+    if (counts || h_sing) SW_HIP(hipStreamSynchronize(s));
+    if (h_sing) *loop->n_singular = int64_t(*h_sing);
     return SWARM_OK;
+}
+
+}  // namespace
+}  // namespace swarm
+
+extern "C" {
+
+int swarm_protocol_run(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
+                       const int32_t *col, const int32_t *hear_row_ptr, const int32_t *hear_col,
+                       const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
+                       double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                       int32_t n_kill, int64_t *counts, void *stream) {
+    return swarm::run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
+                            timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, nullptr, stream);
+}
+
+int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
+                          const int32_t *col, const int32_t *hear_row_ptr, const int32_t *hear_col,
+                          const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
+                          double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                          int32_t n_kill, double pull_frac, int64_t *counts, int64_t *traffic, void *stream) {
+    return swarm::run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
+                            timeout, jitter, seed, kill_ticks, n_kill, pull_frac, counts, traffic, nullptr, stream);
+}
+
+int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                      const int32_t *row_ptr, const int32_t *col, const int32_t *hear_row_ptr,
+                      const int32_t *hear_col, const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0,
+                      int32_t ticks, double dt, double timeout, double jitter, uint64_t seed,
+                      const int64_t *kill_ticks, int32_t n_kill, double pull_frac, double *vel, double *target,
+                      uint8_t *has_target, int64_t m, const double *obstacles, const int32_t *sense_row_ptr,
+                      const int32_t *sense_col, double max_speed, double *trace, int32_t trace_every,
+                      int64_t *counts, int64_t *n_singular, void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(n >= 0 && n < (int64_t(1) << 31) && m >= 0 && ticks >= 0, "sizes out of range");
+    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
+    SW_ARG(n == 0 || (pos && pos_prev && vel && target && has_target && sense_row_ptr), "NULL agent array");
+    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
+    SW_ARG(trace_every >= 0, "trace_every must not be negative");
+    SW_ARG(n == 0 || trace_every == 0 || ticks / trace_every == 0 || trace != nullptr, "trace is NULL");
+    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
+        const uintptr_t a = reinterpret_cast<uintptr_t>(pos), b = reinterpret_cast<uintptr_t>(pos_prev);
+        SW_ARG((a > b ? a - b : b - a) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
+        SW_ARG((a & 15) == 0 && (b & 15) == 0, "pos / pos_prev are not 16-byte aligned");
+    }
+    if (n_singular) *n_singular = 0;
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, sense_row_ptr, sense_col, max_speed,
+                        trace, trace_every, n_singular};
+    return run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt, timeout,
+                     jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream);
 }
 
 }  // extern "C"

@@ -674,6 +674,143 @@ class Swarm:
         self.fsm_tick += int(ticks)
         return counts
 
+    # ------------------------------------------------------------------ coupled update loop (U1)
+    def _motion_state(self):
+        """vel / target / has_target, created as physics_step creates them."""
+        if not hasattr(self, "vel"):
+            n, dev = self.n, self.device
+            self.vel = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+            self.target = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+            self.has_target = torch.zeros(n, dtype=torch.uint8, device=dev)
+
+    def _target_rows(self, index):
+        """Storage rows of the agents `index` names in INPUT numbering (None: every agent, input order)."""
+        if index is not None:
+            idx = np.atleast_1d(np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index))
+            if idx.ndim != 1 or idx.dtype.kind not in "iu":
+                raise ValueError("index must be a 1-D array of agent indices (input order)")
+            if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= self.n):
+                raise ValueError(f"index out of range for {self.n} agents")
+        else:
+            idx = None
+        if self.layout == "input":
+            return None if idx is None else torch.as_tensor(idx.astype(np.int64), device=self.device)
+        inv = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        inv[self.perm.long()] = torch.arange(self.n, dtype=torch.int64, device=self.device)
+        return inv if idx is None else inv[torch.as_tensor(idx.astype(np.int64), device=self.device)]
+
+    def set_target(self, x, y, index=None):
+        """SwarmAgent.set_target (agent.py:56-57), batched: agent index[k] (INPUT numbering; None = every
+        agent, in input order) gets the target (x[k], y[k]); scalars go to every agent named."""
+        count = self.n if index is None else int(np.atleast_1d(np.asarray(
+            index.cpu() if isinstance(index, torch.Tensor) else index)).shape[0])
+        xy = []
+        for name, v in (("x", x), ("y", y)):
+            a = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v, np.float64)
+            if a.ndim == 0:
+                a = np.full(count, float(a))
+            if a.shape != (count,):
+                raise ValueError(f"{name}: expected {count} values, got shape {tuple(a.shape)}")
+            xy.append(a)
+        rows = self._target_rows(index)
+        self._motion_state()
+        t = torch.as_tensor(np.stack(xy, 1), device=self.device)
+        if rows is None:
+            self.target.copy_(t)
+            self.has_target.fill_(1)
+        else:
+            self.target[rows] = t
+            self.has_target[rows] = 1
+        return self
+
+    def clear_target(self, index=None):
+        """target = None for the agents `index` names (INPUT numbering; None = every agent): they stop
+        where they are until a leader position gives them a slot again."""
+        rows = self._target_rows(index)
+        self._motion_state()
+        if rows is None or index is None:
+            self.target.zero_()
+            self.has_target.zero_()
+        else:
+            self.target[rows] = 0.0
+            self.has_target[rows] = 0
+        return self
+
+    def update_loop(self, ticks: int, *, obstacles=None, sensors=None, kill_ticks=(), dt: float = 0.1,
+                    timeout: float = 3.0, jitter: float = 0.2, seed: int = 0, max_speed: float = 5.0,
+                    mode: str = "hybrid", pull_frac: float = 0.125, trace_every: int = 0) -> dict:
+        """`ticks` ticks of the reference's update_loop (agent.py:67-81) for every agent, in one call on the
+        GPU (contract U1; swarm_update_loop): each tick protocol_run's tick, then a physics step in which
+        every alive agent uses its own FSM state -- a FOLLOWER steers to the V slot behind the leader
+        position its last accepted heartbeat carried (f32, up to ten ticks old), an ELECTION_WAIT agent or
+        a new LEADER keeps its last target, dead agents stay frozen.  A heartbeat carries the position its
+        sender had when it packed it, one physics step before the tick that receives it.
+        obstacles: (m, 3) [x, y, r]; sensors: (row_ptr, col) over storage indices, fixed for the call
+        (default: the neighbour graph); the other keywords as protocol_run / physics_step.  Uses self.fsm /
+        self.fsm_tick as protocol_run does and advances self.fsm_tick, so calls chain into one run.
+        self.pos_prev holds the positions one tick before self.pos (what the heartbeats in flight carry);
+        it is kept from the previous update_loop call while self.pos is still that call's tensor, untouched
+        since -- when anything else has moved or replaced self.pos, or there was no previous call, it
+        starts as a copy of self.pos.
+        Returns {"counts": (ticks x 4) as protocol_run, "singular": zero distances over all ticks} and,
+        with trace_every = k > 0, "trace": (ticks // k, n, 2) positions after every k-th tick of the call,
+        storage order."""
+        ticks, trace_every = int(ticks), int(trace_every)
+        if mode not in ("push", "pull", "hybrid"):
+            raise ValueError(f"unknown mode {mode!r}")
+        if ticks < 0:
+            raise ValueError("ticks must not be negative")
+        if trace_every < 0:
+            raise ValueError("trace_every must not be negative")
+        if self.row_ptr is None:
+            raise RuntimeError("no neighbour graph: call build_graph() or set_graph()")
+        dev, n = self.device, self.n
+        if not hasattr(self, "fsm"):
+            self.protocol_reset()
+        self._motion_state()
+        srp, scol = (self.row_ptr, self.col) if sensors is None else \
+            (_to(sensors[0], torch.int32, dev), _to(sensors[1], torch.int32, dev))
+        if srp.numel() != n + 1:
+            raise ValueError(f"sensors: row_ptr needs {n + 1} entries, got {srp.numel()}")
+        obs = torch.zeros((0, 3), dtype=torch.float64, device=dev) if obstacles is None else \
+            _to(obstacles, torch.float64, dev).reshape(-1, 3).contiguous()
+        k = getattr(self, "_pos_prev_key", None)
+        if k is None or k[0] is not self.pos or k[1] != self.pos._version or not hasattr(self, "pos_prev"):
+            self.pos_prev = self.pos.clone()
+        f = self.fsm
+        fs = _lib.Fsm(*[_lib.ptr(t) if n else None for t in
+                        (self.state, self.leader, f["last_hb"], f["wait_start"], f["delay"], f["leader_pos"],
+                         f["has_leader_pos"], f["alive"], f["outbox"])])
+        kt = np.ascontiguousarray(np.asarray(kill_ticks, np.int64))
+        h = getattr(self, "_hear", None) or (self.row_ptr, self.col)
+        hear = (None, None) if mode == "pull" or n == 0 else \
+            (_lib.ptr(h[0], torch.int32), _lib.ptr(h[1], torch.int32) if h[1].numel() else None)
+        counts = np.zeros((ticks, 4), np.int64)
+        frames = ticks // trace_every if trace_every else 0
+        trace = torch.empty((frames, n, 2), dtype=torch.float64, device=dev) if trace_every else None
+        sing = ctypes.c_int64(0)
+        p = lambda t: _lib.ptr(t) if n else None  # noqa: E731
+        with torch.cuda.device(dev):
+            rc = _lib.lib().swarm_update_loop(
+                _lib.ctx(), n, p(self.ids), p(self.pos), p(self.pos_prev), _lib.ptr(self.row_ptr, torch.int32),
+                _lib.ptr(self.col, torch.int32) if self.n_edges else None, *hear, p(self.tick_off),
+                ctypes.byref(fs), self.fsm_tick, ticks, float(dt), float(timeout), float(jitter),
+                ctypes.c_uint64(int(seed)), kt.ctypes.data_as(ctypes.c_void_p) if kt.size else None, kt.size,
+                float(pull_frac) if mode == "hybrid" else -1.0, p(self.vel), p(self.target), p(self.has_target),
+                obs.shape[0], _lib.ptr(obs) if obs.numel() else None, _lib.ptr(srp, torch.int32),
+                _lib.ptr(scol, torch.int32) if scol.numel() else None, float(max_speed),
+                _lib.ptr(trace) if frames and n else None, trace_every, counts.ctypes.data_as(ctypes.c_void_p),
+                ctypes.byref(sing), _lib.stream())
+        if n and ticks:
+            self._cindex = None  # agents moved: the storage order is no longer their cell order
+        self._pos_prev_key = (self.pos, self.pos._version)
+        _lib.check(rc)
+        self.fsm_tick += ticks
+        out = {"counts": counts, "singular": sing.value}
+        if trace_every:
+            out["trace"] = trace
+        return out
+
     # ------------------------------------------------------------------ views / bridge
     def to_input_order(self, storage_tensor) -> np.ndarray:
         """Host copy of a per-agent tensor re-ordered to the caller's input numbering."""

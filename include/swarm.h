@@ -583,6 +583,41 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
                           double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
                           int32_t n_kill, double pull_frac, int64_t *counts, int64_t *traffic, void *stream);
 
+/*
+ * The coupled update loop (agent.py:67-81: each tick _process_logic, then _update_physics), for the
+ * whole swarm, ticks t0+1 .. t0+ticks in one call (contract U1).  dt is both the FSM's clock step and
+ * the physics step (the reference's period).  With P_k the positions after the physics of tick k, tick t:
+ *   kills, receive, logic   swarm_protocol_run_ex's tick (same arguments, same meaning), except that a
+ *             HEARTBEAT received at tick t carries the f32-rounded position its sender had when it sent
+ *             it during tick t-1, P_{t-2} (the payload is packed inside _process_logic, before that
+ *             tick's physics);
+ *   physics   every alive agent senses its row of sense_row_ptr / sense_col (CSR order, dead agents
+ *             included as bodies at rest) and the m obstacles at the snapshot P_{t-1} and runs
+ *             swarm_physics_step's arithmetic with its own FSM state as the tick's logic left it: a
+ *             FOLLOWER with has_leader_pos retargets the V slot behind its own leader_pos (stored in
+ *             target / has_target); any other agent keeps the target it had (an ELECTION_WAIT agent
+ *             and a new LEADER keep chasing their last slot); without a target it keeps position and
+ *             velocity.  Dead agents run neither half: position, velocity and target stay frozen.
+ * pos / pos_prev (n x 2 f64, 16-byte aligned, not overlapping): in, P_{t0} and P_{t0-1} (what the
+ * heartbeats in flight at t0 carry; a copy of pos for a fresh run); out, P_{t0+ticks} and
+ * P_{t0+ticks-1}, for either parity of ticks -- so a run split into chunks is the same run.  vel /
+ * target / has_target / obstacles / max_speed: as swarm_physics_step.  trace (device, frames x n x 2
+ * f64, frames = ticks / trace_every; ignored when trace_every == 0): frame f = P_{t0+(f+1) trace_every}.
+ * counts (host, ticks x 4, may be NULL) as swarm_protocol_run; n_singular (host, may be NULL) as
+ * swarm_physics_step, summed over the ticks.  The FSM's records are packed once and unpacked once; no
+ * host wait inside the loop, one at the end when counts or n_singular is given.  n == 0 or ticks == 0:
+ * nothing is read or written (counts zeroed, *n_singular = 0).  Arguments are checked before anything is
+ * launched (SWARM_ERR_ARG).  The neighbour lists are fixed for the call (no re-sensing).
+ */
+int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                      const int32_t *row_ptr, const int32_t *col, const int32_t *hear_row_ptr,
+                      const int32_t *hear_col, const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0,
+                      int32_t ticks, double dt, double timeout, double jitter, uint64_t seed,
+                      const int64_t *kill_ticks, int32_t n_kill, double pull_frac, double *vel, double *target,
+                      uint8_t *has_target, int64_t m, const double *obstacles, const int32_t *sense_row_ptr,
+                      const int32_t *sense_col, double max_speed, double *trace, int32_t trace_every,
+                      int64_t *counts, int64_t *n_singular, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
