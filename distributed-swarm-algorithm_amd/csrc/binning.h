@@ -15,12 +15,6 @@
 
 namespace swarm {
 
-struct Grid {
-    double xmin, ymin, xmax, ymax;
-    double cell, inv_cell;
-    int64_t ncx, ncy;
-};
-
 __device__ __forceinline__ int64_t cell_coord(double v, double vmin, double inv_cell, int64_t nc) {
     double f = floor((v - vmin) * inv_cell);
     if (!(f >= 0.0)) return 0;            // also catches NaN
@@ -94,6 +88,25 @@ static __global__ __launch_bounds__(kBlock) void k_cell_offsets(const uint32_t *
     }
 }
 
+// The same offsets by search, one thread per cell: cell_off[c] = the first sorted position whose key is
+// >= c.  k_cell_offsets has the thread at a key boundary fill every empty cell up to the next key, one store
+// after the other: right when most cells are occupied, but a grid grown far beyond the agents (the sensed
+// update loop's: the entry box plus the run's reach, 100 units a side for 200 ticks) leaves the first and
+// the last thread ~1e5 cells of margin each (1.4 of 4.8 ms per tick at 10M agents).
+static __global__ __launch_bounds__(kBlock) void k_cell_offsets_search(const uint32_t *__restrict__ skeys,
+                                                                      int64_t n, int64_t ncells,
+                                                                      uint32_t *__restrict__ off) {
+    for (int64_t c = int64_t(blockIdx.x) * kBlock + threadIdx.x; c <= ncells; c += int64_t(gridDim.x) * kBlock) {
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (int64_t(skeys[mid]) < c) lo = mid + 1;
+            else hi = mid;
+        }
+        off[c] = uint32_t(lo);
+    }
+}
+
 // Cells of side >= `cell` over g's bounding box (enlarged until the grid has at most max_cells).
 static inline void shape_grid(Grid *g, double cell, int64_t max_cells) {
     double c = cell > 0 ? cell : 1.0;
@@ -139,9 +152,10 @@ static inline int make_grid(swarm_ctx *ctx, int64_t n, const double *pos, double
 
 // Sort agents by cell.  On return *sorted_idx (device, n) lists agent indices cell by cell
 // (ascending index within a cell: the radix sort is stable) and *cell_off (device,
-// ncells + 1) is the exclusive prefix.
+// ncells + 1) is the exclusive prefix.  sparse_grid: the offsets by search (k_cell_offsets_search), for a grid
+// with wide empty margins.
 static inline int bin_agents(swarm_ctx *ctx, int64_t n, const double *pos, const Grid &g,
-                             int32_t **sorted_idx, uint32_t **cell_off, hipStream_t s) {
+                             int32_t **sorted_idx, uint32_t **cell_off, hipStream_t s, bool sparse_grid = false) {
     const int64_t ncells = g.ncx * g.ncy;
     uint32_t *kin, *kout, *off;
     int32_t *vin, *vout;
@@ -160,8 +174,12 @@ static inline int bin_agents(swarm_ctx *ctx, int64_t n, const double *pos, const
     void *tmp;
     SW_ALLOC(tmp, ctx, S_CUB_TMP, tmp_bytes);
     SW_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kin, kout, vin, vout, int(n), 0, end_bit, s));
-    hipLaunchKernelGGL(k_cell_offsets, dim3(grid_for(n + 1, kBlock, 8192)), dim3(kBlock), 0, s, kout, n,
-                       ncells, off);
+    if (sparse_grid)
+        hipLaunchKernelGGL(k_cell_offsets_search, dim3(grid_for(ncells + 1, kBlock, 8192)), dim3(kBlock), 0, s, kout,
+                           n, ncells, off);
+    else
+        hipLaunchKernelGGL(k_cell_offsets, dim3(grid_for(n + 1, kBlock, 8192)), dim3(kBlock), 0, s, kout, n,
+                           ncells, off);
     SW_LAUNCHED();
     *sorted_idx = vout;
     *cell_off = off;

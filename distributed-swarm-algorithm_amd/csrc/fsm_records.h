@@ -50,4 +50,32 @@ int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const L
                         const double *obstacles, const int32_t *row_ptr, const int32_t *col, double dt,
                         double max_speed, unsigned long long *singular, hipStream_t s);
 
+// The sensed loop (contract U1-S; physics.hip): the separation neighbours of every tick are sensed from that
+// tick's snapshot.  One LoopSense per call: the call's grid, the tick's binning and the device's verdict.
+struct LoopSense {
+    Grid g;                   // one grid for the call: the entry bounding box grown by the run's reach
+    double r2;                // sense_radius squared
+    double2 *psort;           // the tick's snapshot in cell-sorted order
+    int32_t *sorted;          // the tick's binning: storage indices cell by cell, and the cells' offsets
+    uint32_t *off;
+    unsigned long long *st;   // device: [0] 0, or 1 + the call's first tick (from 0) refused for its window
+                              // work; [2], [3] that tick's candidate pairs (a double's bits), largest window
+};
+// The call's grid from the bounding box of `pos` (one host wait; non-finite positions: SWARM_ERR_ARG with
+// nothing written) and the verdict words cleared.
+int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t ticks, double dt,
+                     double max_speed, LoopSense *ls, hipStream_t s);
+// Tick k of the call (from 0), queued on `s`: the snapshot binned, its window work judged on the device
+// against swarm_build_rgg's limits, the cell-sorted copy of the snapshot.
+int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s);
+// The error of a call whose verdict words h (st read back) report a refused tick: "too dense", the absolute
+// tick and the window figures; returns SWARM_ERR_RANGE.
+int loop_sense_refusal(const unsigned long long *h, int64_t tick);
+// launch_physics_loop with the row of a sensor CSR replaced by the agent's 3 x 3 cell window of
+// loop_sense_tick's binning (the snapshot is read through ls.psort); does nothing once a tick was refused.
+int launch_physics_loop_sensed(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, double *pos_out,
+                               double *vel, double *target, uint8_t *has_target, int64_t m,
+                               const double *obstacles, const LoopSense &ls, double dt, double max_speed,
+                               unsigned long long *singular, hipStream_t s);
+
 }  // namespace swarm

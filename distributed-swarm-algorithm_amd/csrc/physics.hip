@@ -519,6 +519,115 @@ __global__ __launch_bounds__(kBlock) void k_physics_sensed(
     count_singular(sing, st + 1);
 }
 
+// ---- the sensed loop's step (contract U1-S): k_physics_loop's agent, k_physics_sensed's neighbours ----
+//
+// k_physics_sensed's nine-way merge as a function: the separation force on agent i at (px, py) from its
+// 3 x 3 cell window, the sensed neighbours (s2 <= r2) applied in ascending storage index.  The same
+// statements on the same operands, hence the same bits.  (k_physics_sensed keeps its body written out:
+// routed through this function, whole or split into the window's opening and its merge, the compiler
+// scheduled it differently -- 1 155 / 1 160 instructions for 1 165 -- and S1's figures were measured on
+// the form it has.)
+__device__ __forceinline__ SepAcc window_separation(int64_t i, double px, double py, const Grid &g, double r2,
+                                                    const int32_t *__restrict__ sorted_idx,
+                                                    const uint32_t *__restrict__ off,
+                                                    const double2 *__restrict__ psort, unsigned long long sing) {
+    const int64_t cx = cell_coord(px, g.xmin, g.inv_cell, g.ncx);
+    const int64_t cy = cell_coord(py, g.ymin, g.inv_cell, g.ncy);
+    uint32_t cur[9], end[9];
+    int32_t head[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int64_t yy = cy + (k / 3) - 1, xx = cx + (k % 3) - 1;
+        const bool in = yy >= 0 && yy < g.ncy && xx >= 0 && xx < g.ncx;
+        const int64_t c = in ? yy * g.ncx + xx : 0;
+        cur[k] = in ? off[c] : 0u;
+        end[k] = in ? off[c + 1] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kNoHead;
+    double fsx = 0.0, fsy = 0.0;
+    for (;;) {
+        int32_t j = head[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) j = head[k] < j ? head[k] : j;
+        if (j == kNoHead) break;
+        uint32_t q = 0, e = 0;  // the run that holds j (indices are distinct: exactly one)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const bool hit = head[k] == j;
+            q = hit ? cur[k] : q;
+            e = hit ? end[k] : e;
+        }
+        const double2 o = psort[q];
+        const uint32_t qn = q + 1;
+        const int32_t hn = qn < e ? sorted_idx[qn] : kNoHead;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const bool hit = head[k] == j;
+            cur[k] = hit ? qn : cur[k];
+            head[k] = hit ? hn : head[k];
+        }
+        if (j == int32_t(i)) continue;
+        const double ex = px - o.x, ey = py - o.y;
+        const double s2 = ex * ex + ey * ey;
+        if (s2 <= r2) {
+            const SepAcc r = separation_term(ex, ey, s2, SepAcc{fsx, fsy, sing});
+            fsx = r.x;
+            fsy = r.y;
+            sing = r.sing;
+        }
+    }
+    return SepAcc{fsx, fsy, sing};
+}
+
+// A tick's physics of swarm_update_loop_sensed, after the tick's FSM kernel: k_physics_sensed's thread
+// mapping (cell-sorted order over the cell-sorted copy of the snapshot) with the agent's state taken from
+// the run's records as k_physics_loop takes it -- the flag word of the 8-byte record, a follower's leader
+// position from its own LRec.  A dead agent's position is copied through and nothing else of it is written;
+// it is still binned, so the others sense it as a body at rest.  st[0] != 0 (a tick refused for its window
+// work): nothing is read or written -- the call is all or nothing and its caller restores the state.
+// Occupancy: the obstacles' 24 KiB of LDS admit six workgroups a CU, six waves a SIMD, which 80 VGPRs would
+// fill; the merge's 27 cursor registers and the fp64 temporaries take 93, and bounded to six waves
+// (__launch_bounds__(kBlock, 6)) the compiler spills ten registers to 44 bytes of scratch a lane -- so, as
+// k_physics_sensed, no occupancy bound: 93 VGPRs, five waves a SIMD, no scratch (the bounded form
+// was compiled, not timed).
+__global__ __launch_bounds__(kBlock) void k_physics_loop_sensed(
+    int64_t n, const int32_t *__restrict__ ids, const uint2 *__restrict__ rec, const LRec *__restrict__ lrec,
+    double2 *__restrict__ pout, double2 *__restrict__ vel, double2 *__restrict__ tgt, uint8_t *__restrict__ has_t,
+    int64_t m, const double *__restrict__ obs, Grid g, double r2, const int32_t *__restrict__ sorted_idx,
+    const uint32_t *__restrict__ off, const double2 *__restrict__ psort, double dt, double max_speed,
+    const unsigned long long *__restrict__ st, unsigned long long *__restrict__ singular) {
+    __shared__ double s_obs[kObsLds * 3];
+    if (st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    unsigned long long sing = 0;
+    for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
+        const int64_t q0 = base + threadIdx.x;
+        const bool valid = q0 < n;
+        int64_t i = 0;
+        double px = 0, py = 0, frx = 0.0, fry = 0.0;
+        bool moving = false;
+        double2 t = make_double2(0, 0);
+        if (valid) {
+            i = sorted_idx[q0];
+            const double2 p = psort[q0];
+            px = p.x;
+            py = p.y;
+            moving = formation_target_loop(i, ids, rec[i].x, lrec, tgt, has_t, t);
+        }
+        obstacle_forces(s_obs, m, obs, moving, px, py, frx, fry, sing);
+        if (!moving) {  // dead or without a target: its position in the output buffer too
+            if (valid) pout[i] = make_double2(px, py);
+            continue;
+        }
+        double fax = 0.0, fay = 0.0;
+        attraction(px, py, t, fax, fay);
+        const SepAcc sep = window_separation(i, px, py, g, r2, sorted_idx, off, psort, sing);
+        sing = sep.sing;
+        integrate(i, px, py, fax, fay, frx, fry, sep.x, sep.y, dt, max_speed, vel, pout);
+    }
+    count_singular(sing, singular);
+}
+
 }  // namespace
 
 int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, const double *pos_in,
@@ -529,6 +638,75 @@ int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const L
                        reinterpret_cast<const double2 *>(pos_in), reinterpret_cast<double2 *>(pos_out),
                        reinterpret_cast<double2 *>(vel), reinterpret_cast<double2 *>(target), has_target, m,
                        obstacles, row_ptr, col, dt, max_speed, singular);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
+// The grid of a call that moves its agents for `steps` steps: no agent moves more than |max_speed * dt| a
+// step, so the entry bounding box grown by the run's reach holds every finite position of every step
+// (cell_coord clamps the rest to an edge cell, which keeps two agents within R in adjacent cells).  One host
+// wait; non-finite positions are refused here, before anything is written.
+static int make_run_grid(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t steps,
+                         double dt, double max_speed, Grid *g, hipStream_t s) {
+    const double cell = (sense_radius < 2.0 ? sense_radius : 2.0) * (1.0 + 1e-9);
+    const int64_t cap4 = 4 * n + 1024, max_cells = cap4 < (int64_t(1) << 31) ? cap4 : (int64_t(1) << 31);
+    const int rc = make_grid(ctx, n, pos, cell, max_cells, g, s);
+    if (rc) return rc;
+    double reach = double(steps) * std::fabs(max_speed * dt);
+    if (!(reach < 1e12)) reach = 1e12;  // any box is exact; beyond it the agents share the edge cells
+    g->xmin -= reach;
+    g->ymin -= reach;
+    g->xmax += reach;
+    g->ymax += reach;
+    shape_grid(g, cell, max_cells);
+    return SWARM_OK;
+}
+
+int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t ticks, double dt,
+                     double max_speed, LoopSense *ls, hipStream_t s) {
+    const int rc = make_run_grid(ctx, n, pos, sense_radius, ticks, dt, max_speed, &ls->g, s);
+    if (rc) return rc;
+    ls->r2 = sense_radius * sense_radius;
+    ls->sorted = nullptr;
+    ls->off = nullptr;
+    SW_ALLOC(ls->psort, ctx, S_SENSE_SORTED, size_t(n) * 16);
+    SW_ALLOC(ls->st, ctx, S_SENSE_STATE, 64);
+    SW_HIP(hipMemsetAsync(ls->st, 0, 32, s));
+    return SWARM_OK;
+}
+
+int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s) {
+    double *acc;
+    int rc;
+    // the call's grid reaches far beyond the agents (the run's reach on every side): offsets by search
+    if ((rc = bin_agents(ctx, n, pos_in, ls->g, &ls->sorted, &ls->off, s, true))) return rc;
+    if ((rc = launch_window_work(ctx, ls->off, ls->g, s, &acc))) return rc;
+    hipLaunchKernelGGL(k_sense_verdict, dim3(1), dim3(1), 0, s, acc, ls->st, k);
+    SW_LAUNCHED();
+    hipLaunchKernelGGL(k_sorted_positions, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s,
+                       reinterpret_cast<const double2 *>(pos_in), n, ls->sorted, ls->psort);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
+int loop_sense_refusal(const unsigned long long *h, int64_t tick) {
+    double pairs;
+    memcpy(&pairs, h + 2, 8);
+    char what[112];
+    snprintf(what, sizeof(what), "agents too dense to sense at tick %lld (nothing of the call is kept)",
+             static_cast<long long>(tick));
+    set_window_work_error(what, pairs, h[3]);
+    return SWARM_ERR_RANGE;
+}
+
+int launch_physics_loop_sensed(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, double *pos_out,
+                               double *vel, double *target, uint8_t *has_target, int64_t m,
+                               const double *obstacles, const LoopSense &ls, double dt, double max_speed,
+                               unsigned long long *singular, hipStream_t s) {
+    hipLaunchKernelGGL(k_physics_loop_sensed, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids, rec, lrec,
+                       reinterpret_cast<double2 *>(pos_out), reinterpret_cast<double2 *>(vel),
+                       reinterpret_cast<double2 *>(target), has_target, m, obstacles, ls.g, ls.r2, ls.sorted, ls.off,
+                       ls.psort, dt, max_speed, ls.st, singular);
     SW_LAUNCHED();
     return SWARM_OK;
 }
@@ -590,22 +768,11 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
         if (n_singular) *n_singular = 0;
         return SWARM_OK;
     }
-    // One grid for the whole call: no agent moves more than |max_speed * dt| a step, so the entry bounding
-    // box grown by the run's reach holds every finite position of every step (cell_coord clamps the rest
-    // to an edge cell, which keeps two agents within R in adjacent cells).  Host wait 1 of 2; non-finite
-    // positions are refused here, before anything is written.
-    const double cell = (sense_radius < 2.0 ? sense_radius : 2.0) * (1.0 + 1e-9);
-    const int64_t cap4 = 4 * n + 1024, max_cells = cap4 < (int64_t(1) << 31) ? cap4 : (int64_t(1) << 31);
+    // One grid for the whole call (make_run_grid).  Host wait 1 of 2; non-finite positions are refused here,
+    // before anything is written.
     Grid g;
-    int rc = make_grid(ctx, n, pos, cell, max_cells, &g, s);
+    int rc = make_run_grid(ctx, n, pos, sense_radius, steps, dt, max_speed, &g, s);
     if (rc) return rc;
-    double reach = double(steps) * std::fabs(max_speed * dt);
-    if (!(reach < 1e12)) reach = 1e12;  // any box is exact; beyond it the agents share the edge cells
-    g.xmin -= reach;
-    g.ymin -= reach;
-    g.xmax += reach;
-    g.ymax += reach;
-    shape_grid(&g, cell, max_cells);
     double2 *other, *psort;
     unsigned long long *st;
     SW_ALLOC(other, ctx, S_SENSE_POS, size_t(n) * 16);

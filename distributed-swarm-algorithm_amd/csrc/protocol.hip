@@ -39,8 +39,12 @@
 // swarm_update_loop (contract U1, agent.py:67-81) runs the same ticks, each followed by the physics step
 // of that tick (physics.hip k_physics_loop, on the run's records): the host loop below is shared
 // (run_ticks), the tick kernels are the same and read the heartbeat positions from the lagged one of the
-// loop's two position buffers.
+// loop's two position buffers.  swarm_update_loop_sensed (contract U1-S) is that loop with the separation
+// neighbours of every tick sensed from the tick's snapshot (physics.hip k_physics_loop_sensed): per tick the
+// snapshot is binned and its window work judged before the tick kernel, the tick kernels are untouched, and a
+// refused tick makes the call restore every caller array on the device (k_restore_refused: all or nothing).
 #include <cmath>
+#include <cstring>
 
 #include "fsm_records.h"
 
@@ -810,7 +814,27 @@ struct LoopArgs {
     double *trace;  // frames x n x 2, or NULL
     int32_t trace_every;
     int64_t *n_singular;  // host, may be NULL
+    double sense_radius;  // > 0: contract U1-S, every tick senses its neighbours (sense_rp / sense_col unused)
+    int64_t *refused_tick;  // U1-S; host, may be NULL
 };
+
+// dst <- src (bytes) when a tick of the sensed loop was refused (st[0] != 0), else nothing: the entry
+// snapshot of one caller array put back, on the device, so that the call needs no host wait to decide.
+__global__ __launch_bounds__(kBlock) void k_restore_refused(const unsigned long long *__restrict__ st,
+                                                           uint8_t *__restrict__ dst,
+                                                           const uint8_t *__restrict__ src, size_t bytes) {
+    if (st[0] == 0) return;
+    const size_t stride = size_t(gridDim.x) * kBlock, first = size_t(blockIdx.x) * kBlock + threadIdx.x;
+    size_t done = 0;
+    if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 7) == 0) {
+        const size_t words = bytes / 8;
+        unsigned long long *d = reinterpret_cast<unsigned long long *>(dst);
+        const unsigned long long *q = reinterpret_cast<const unsigned long long *>(src);
+        for (size_t w = first; w < words; w += stride) d[w] = q[w];
+        done = words * 8;
+    }
+    for (size_t b = done + first; b < bytes; b += stride) dst[b] = src[b];
+}
 
 // a <-> b, element-wise (an odd number of ticks leaves the newest positions in the caller's pos_prev)
 __global__ __launch_bounds__(kBlock) void k_swap_positions(int64_t n, double2 *__restrict__ a, double2 *__restrict__ b) {
@@ -844,6 +868,36 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
         return SWARM_OK;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
+    // U1-S: the call's grid (the loop's one host wait before its end; non-finite positions are refused here),
+    // then the caller's arrays as they are now, put back on the device if a tick is refused -- the ticks after
+    // a refused one are already queued and run on the records, so the call is all or nothing
+    const bool sensed = loop && loop->sense_radius > 0.0;
+    LoopSense ls{};
+    struct Kept {
+        void *p;
+        size_t bytes, at;
+    } kept[14];
+    int n_kept = 0;
+    uint8_t *snap = nullptr;
+    if (sensed) {
+        const int rc = loop_sense_begin(ctx, n, loop->pos, loop->sense_radius, ticks, dt, loop->max_speed, &ls, s);
+        if (rc) return rc;
+        const size_t un = size_t(n);
+        const Kept all[14] = {{loop->pos, un * 16, 0},       {loop->pos_prev, un * 16, 0},  {loop->vel, un * 16, 0},
+                              {loop->target, un * 16, 0},    {fsm->last_hb, un * 8, 0},     {fsm->wait_start, un * 8, 0},
+                              {fsm->delay, un * 8, 0},       {fsm->leader_pos, un * 8, 0},  {fsm->leader, un * 4, 0},
+                              {fsm->outbox, un * 2, 0},      {loop->has_target, un, 0},     {fsm->state, un, 0},
+                              {fsm->alive, un, 0},           {fsm->has_leader_pos, un, 0}};
+        size_t total = 0;
+        for (const Kept &k : all) {
+            kept[n_kept] = k;
+            kept[n_kept++].at = total;
+            total += (k.bytes + 15) & ~size_t(15);
+        }
+        SW_ALLOC(snap, ctx, S_LOOP_SNAP, total);
+        for (int q = 0; q < n_kept; ++q)
+            SW_HIP(hipMemcpyAsync(snap + kept[q].at, kept[q].p, kept[q].bytes, hipMemcpyDeviceToDevice, s));
+    }
     unsigned long long *d_cnt;  // per tick: kShards x 4 partial counters, then the 4 sums
     const size_t part_bytes = size_t(ticks) * kShards * 4 * 8;
     const size_t tr_bytes = size_t(kShards) * kTraffic * 8;
@@ -965,6 +1019,10 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
             hipLaunchKernelGGL(k_kill_leaders, dim3(grid), dim3(kBlock), 0, s, n, f.rec);
             SW_LAUNCHED();
         }
+        if (sensed) {  // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell
+            const int rc = loop_sense_tick(ctx, n, cur, int32_t(t - t0 - 1), &ls, s);
+            if (rc) return rc;
+        }
         const uint8_t *ob_in = fsm->outbox + size_t((t - 1) & 1) * size_t(n);
         uint8_t *ob_out = fsm->outbox + size_t(t & 1) * size_t(n);
         unsigned long long *cnt = d_cnt + size_t(t - t0 - 1) * kShards * 4;
@@ -990,9 +1048,13 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
         }
         SW_LAUNCHED();
         if (loop) {  // the tick's physics: P_{t-1} -> P_t over the lagged buffer, then the roles swap
-            const int rc = launch_physics_loop(n, ids, f.rec, f.lrec, cur, lag, loop->vel, loop->target,
-                                               loop->has_target, loop->m, loop->obstacles, loop->sense_rp,
-                                               loop->sense_col, dt, loop->max_speed, d_sing, s);
+            const int rc =
+                sensed ? launch_physics_loop_sensed(n, ids, f.rec, f.lrec, lag, loop->vel, loop->target,
+                                                    loop->has_target, loop->m, loop->obstacles, ls, dt,
+                                                    loop->max_speed, d_sing, s)
+                       : launch_physics_loop(n, ids, f.rec, f.lrec, cur, lag, loop->vel, loop->target,
+                                             loop->has_target, loop->m, loop->obstacles, loop->sense_rp,
+                                             loop->sense_col, dt, loop->max_speed, d_sing, s);
             if (rc) return rc;
             std::swap(cur, lag);
             const int64_t k = t - t0;
@@ -1031,6 +1093,37 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
         SW_HIP(hipMemcpyAsync(hs, d_tr + size_t(kShards) * kTraffic, kTraffic * 8, hipMemcpyDeviceToHost, s));
         SW_HIP(hipStreamSynchronize(s));
         for (int q = 0; q < kTraffic; ++q) traffic[q] = int64_t(hs[q]);
+    }
+    if (sensed) {
+        // a refused tick: every caller array back to its entry bytes (the unpack above included), all on the
+        // device; then the verdict, the singular count and the counts come back through pinned memory in the
+        // call's one final host wait, and the counts reach the caller only when no tick was refused
+        for (int q = 0; q < n_kept; ++q) {
+            hipLaunchKernelGGL(k_restore_refused, dim3(grid_for(int64_t(kept[q].bytes / 8 + 1), kBlock, 4096)),
+                               dim3(kBlock), 0, s, ls.st, static_cast<uint8_t *>(kept[q].p), snap + kept[q].at,
+                               kept[q].bytes);
+            SW_LAUNCHED();
+        }
+        const size_t cnt_bytes = counts ? size_t(ticks) * 4 * 8 : 0;
+        unsigned long long *h = static_cast<unsigned long long *>(pinned(ctx, 64 + cnt_bytes));
+        if (!h) return SWARM_ERR_OOM;
+        SW_HIP(hipMemcpyAsync(h, ls.st, 32, hipMemcpyDeviceToHost, s));
+        SW_HIP(hipMemcpyAsync(h + 4, d_sing, 8, hipMemcpyDeviceToHost, s));
+        if (counts) {
+            hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
+                               int64_t(ticks), d_cnt, d_sum);
+            SW_LAUNCHED();
+            SW_HIP(hipMemcpyAsync(h + 8, d_sum, cnt_bytes, hipMemcpyDeviceToHost, s));
+        }
+        SW_HIP(hipStreamSynchronize(s));
+        if (h[0]) {
+            const int64_t tick = t0 + int64_t(h[0]);
+            if (loop->refused_tick) *loop->refused_tick = tick;
+            return loop_sense_refusal(h, tick);
+        }
+        if (loop->n_singular) *loop->n_singular = int64_t(h[4]);
+        if (counts) memcpy(counts, h + 8, cnt_bytes);
+        return SWARM_OK;
     }
     unsigned long long *h_sing = nullptr;
     if (loop && loop->n_singular) {  // read back with the counts: the run's one host wait
@@ -1095,7 +1188,37 @@ int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos
     }
     if (n_singular) *n_singular = 0;
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, sense_row_ptr, sense_col, max_speed,
-                        trace, trace_every, n_singular};
+                        trace, trace_every, n_singular, 0.0, nullptr};
+    return run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt, timeout,
+                     jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream);
+}
+
+int swarm_update_loop_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                             const int32_t *row_ptr, const int32_t *col, const int32_t *hear_row_ptr,
+                             const int32_t *hear_col, const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0,
+                             int32_t ticks, double dt, double timeout, double jitter, uint64_t seed,
+                             const int64_t *kill_ticks, int32_t n_kill, double pull_frac, double *vel,
+                             double *target, uint8_t *has_target, int64_t m, const double *obstacles,
+                             double sense_radius, double max_speed, double *trace, int32_t trace_every,
+                             int64_t *counts, int64_t *n_singular, int64_t *refused_tick, void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(n >= 0 && n < (int64_t(1) << 31) - 1 && m >= 0 && ticks >= 0, "sizes out of range");
+    SW_ARG(sense_radius > 0 && std::isfinite(sense_radius), "sense_radius must be positive and finite");
+    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
+    SW_ARG(n == 0 || (pos && pos_prev && vel && target && has_target), "NULL agent array");
+    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
+    SW_ARG(trace_every >= 0, "trace_every must not be negative");
+    SW_ARG(n == 0 || trace_every == 0 || ticks / trace_every == 0 || trace != nullptr, "trace is NULL");
+    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
+        const uintptr_t a = reinterpret_cast<uintptr_t>(pos), b = reinterpret_cast<uintptr_t>(pos_prev);
+        SW_ARG((a > b ? a - b : b - a) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
+        SW_ARG((a & 15) == 0 && (b & 15) == 0, "pos / pos_prev are not 16-byte aligned");
+    }
+    if (n_singular) *n_singular = 0;
+    if (refused_tick) *refused_tick = -1;
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
+                        trace, trace_every, n_singular, sense_radius, refused_tick};
     return run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt, timeout,
                      jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream);
 }

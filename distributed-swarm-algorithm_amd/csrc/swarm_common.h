@@ -20,6 +20,13 @@ constexpr int kElectCounters = 4;  // per-round election counters (elect.hip C_C
 
 void set_error(const char *fmt, ...);
 
+// A uniform grid of cells over a bounding box (binning.h; here so that headers without hipCUB can hold one).
+struct Grid {
+    double xmin, ymin, xmax, ymax;
+    double cell, inv_cell;
+    int64_t ncx, ncy;
+};
+
 // Scratch slots owned by a ctx; each grows on demand (never shrinks until destroy).
 enum Slot {
     S_LEADER_B = 0,   // election: second leader buffer (dense)
@@ -60,6 +67,7 @@ enum Slot {
     S_SENSE_POS,      // sensed physics: the second position buffer of the run's double buffering
     S_SENSE_SORTED,   // sensed physics: the step's positions in cell-sorted order
     S_SENSE_STATE,    // sensed physics: stop word, singular count and the refused step's window figures
+    S_LOOP_SNAP,      // sensed update loop: the caller's arrays as they were at entry (restored on a refusal)
     S_NUM
 };
 

@@ -754,7 +754,33 @@ class Swarm:
         starts as a copy of self.pos.
         Returns {"counts": (ticks x 4) as protocol_run, "singular": zero distances over all ticks} and,
         with trace_every = k > 0, "trace": (ticks // k, n, 2) positions after every k-th tick of the call,
-        storage order."""
+        storage order.  update_loop_sensed senses the separation neighbours anew every tick instead."""
+        return self._update_loop(ticks, None, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed, max_speed,
+                                 mode, pull_frac, trace_every)
+
+    def update_loop_sensed(self, ticks: int, sense_radius: float, *, obstacles=None, sensors=None, kill_ticks=(),
+                           dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
+                           max_speed: float = 5.0, mode: str = "hybrid", pull_frac: float = 0.125,
+                           trace_every: int = 0) -> dict:
+        """update_loop with every tick's separation neighbours sensed from that tick's positions (contract
+        U1-S; swarm_update_loop_sensed; the reference's simulator calls update_sensors before every tick): the
+        result of "radius graph of the current storage positions at sense_radius, then update_loop(1,
+        sensors=that graph)" repeated, bit for bit, with no graph built.  The message graph self.row_ptr /
+        self.col is fixed and untouched.  Keywords, self.fsm / self.fsm_tick / self.pos_prev and the returned
+        dict as update_loop; the calls of the two chain into one run.  `sensors` is update_loop's keyword and
+        has no meaning here: anything but None raises ValueError before the device is touched.
+        All or nothing: a tick whose cell windows are too dense raises SwarmError (ERR_RANGE) with the
+        absolute tick in self.last_refused_tick (-1 after a call that went through), and positions, motion
+        state, FSM and self.fsm_tick are what they were before the call (run in chunks to keep the progress
+        up to such a tick)."""
+        if sensors is not None:
+            raise ValueError("update_loop_sensed senses the neighbours itself: sensors must be None")
+        return self._update_loop(ticks, float(sense_radius), obstacles, None, kill_ticks, dt, timeout, jitter, seed,
+                                 max_speed, mode, pull_frac, trace_every)
+
+    def _update_loop(self, ticks, sense_radius, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed,
+                     max_speed, mode, pull_frac, trace_every) -> dict:
+        """update_loop (sense_radius None: the `sensors` lists, fixed) and update_loop_sensed."""
         ticks, trace_every = int(ticks), int(trace_every)
         if mode not in ("push", "pull", "hybrid"):
             raise ValueError(f"unknown mode {mode!r}")
@@ -768,10 +794,11 @@ class Swarm:
         if not hasattr(self, "fsm"):
             self.protocol_reset()
         self._motion_state()
-        srp, scol = (self.row_ptr, self.col) if sensors is None else \
-            (_to(sensors[0], torch.int32, dev), _to(sensors[1], torch.int32, dev))
-        if srp.numel() != n + 1:
-            raise ValueError(f"sensors: row_ptr needs {n + 1} entries, got {srp.numel()}")
+        if sense_radius is None:
+            srp, scol = (self.row_ptr, self.col) if sensors is None else \
+                (_to(sensors[0], torch.int32, dev), _to(sensors[1], torch.int32, dev))
+            if srp.numel() != n + 1:
+                raise ValueError(f"sensors: row_ptr needs {n + 1} entries, got {srp.numel()}")
         obs = torch.zeros((0, 3), dtype=torch.float64, device=dev) if obstacles is None else \
             _to(obstacles, torch.float64, dev).reshape(-1, 3).contiguous()
         k = getattr(self, "_pos_prev_key", None)
@@ -790,17 +817,24 @@ class Swarm:
         trace = torch.empty((frames, n, 2), dtype=torch.float64, device=dev) if trace_every else None
         sing = ctypes.c_int64(0)
         p = lambda t: _lib.ptr(t) if n else None  # noqa: E731
+        refused = ctypes.c_int64(-1)
         with torch.cuda.device(dev):
-            rc = _lib.lib().swarm_update_loop(
-                _lib.ctx(), n, p(self.ids), p(self.pos), p(self.pos_prev), _lib.ptr(self.row_ptr, torch.int32),
-                _lib.ptr(self.col, torch.int32) if self.n_edges else None, *hear, p(self.tick_off),
-                ctypes.byref(fs), self.fsm_tick, ticks, float(dt), float(timeout), float(jitter),
-                ctypes.c_uint64(int(seed)), kt.ctypes.data_as(ctypes.c_void_p) if kt.size else None, kt.size,
-                float(pull_frac) if mode == "hybrid" else -1.0, p(self.vel), p(self.target), p(self.has_target),
-                obs.shape[0], _lib.ptr(obs) if obs.numel() else None, _lib.ptr(srp, torch.int32),
-                _lib.ptr(scol, torch.int32) if scol.numel() else None, float(max_speed),
-                _lib.ptr(trace) if frames and n else None, trace_every, counts.ctypes.data_as(ctypes.c_void_p),
-                ctypes.byref(sing), _lib.stream())
+            head = (_lib.ctx(), n, p(self.ids), p(self.pos), p(self.pos_prev), _lib.ptr(self.row_ptr, torch.int32),
+                    _lib.ptr(self.col, torch.int32) if self.n_edges else None, *hear, p(self.tick_off),
+                    ctypes.byref(fs), self.fsm_tick, ticks, float(dt), float(timeout), float(jitter),
+                    ctypes.c_uint64(int(seed)), kt.ctypes.data_as(ctypes.c_void_p) if kt.size else None, kt.size,
+                    float(pull_frac) if mode == "hybrid" else -1.0, p(self.vel), p(self.target),
+                    p(self.has_target), obs.shape[0], _lib.ptr(obs) if obs.numel() else None)
+            tail = (float(max_speed), _lib.ptr(trace) if frames and n else None, trace_every,
+                    counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(sing))
+            if sense_radius is None:
+                rc = _lib.lib().swarm_update_loop(
+                    *head, _lib.ptr(srp, torch.int32), _lib.ptr(scol, torch.int32) if scol.numel() else None,
+                    *tail, _lib.stream())
+            else:
+                rc = _lib.lib().swarm_update_loop_sensed(*head, float(sense_radius), *tail, ctypes.byref(refused),
+                                                         _lib.stream())
+                self.last_refused_tick = refused.value
         if n and ticks:
             self._cindex = None  # agents moved: the storage order is no longer their cell order
         self._pos_prev_key = (self.pos, self.pos._version)

@@ -607,7 +607,8 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
  * swarm_physics_step, summed over the ticks.  The FSM's records are packed once and unpacked once; no
  * host wait inside the loop, one at the end when counts or n_singular is given.  n == 0 or ticks == 0:
  * nothing is read or written (counts zeroed, *n_singular = 0).  Arguments are checked before anything is
- * launched (SWARM_ERR_ARG).  The neighbour lists are fixed for the call (no re-sensing).
+ * launched (SWARM_ERR_ARG).  The neighbour lists are fixed for the call; swarm_update_loop_sensed senses
+ * them anew every tick.
  */
 int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
                       const int32_t *row_ptr, const int32_t *col, const int32_t *hear_row_ptr,
@@ -617,6 +618,37 @@ int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos
                       uint8_t *has_target, int64_t m, const double *obstacles, const int32_t *sense_row_ptr,
                       const int32_t *sense_col, double max_speed, double *trace, int32_t trace_every,
                       int64_t *counts, int64_t *n_singular, void *stream);
+
+/*
+ * swarm_update_loop with the separation neighbours sensed from the moving positions (contract U1-S; the
+ * reference's simulator calls update_sensors before every tick).  Tick t, with S = P_{t-1} the snapshot its
+ * physics reads: every alive agent i senses each j != i with dx*dx + dy*dy <= sense_radius^2 (fp64, the
+ * products rounded separately: swarm_build_rgg's rule), dead agents and agents without a target included as
+ * bodies at rest, and applies the sensed neighbours in ascending storage index; everything else -- kills,
+ * receive, logic, the heartbeats' P_{t-2}, retargeting, frozen dead agents, the arithmetic, pos / pos_prev,
+ * trace, counts, n_singular -- is swarm_update_loop's, argument for argument.  The message graph (row_ptr /
+ * col and the hearers) is fixed for the call and not touched.  The state after the call is bit-identical to
+ * `ticks` repetitions of swarm_build_rgg(pos, sense_radius) + swarm_update_loop(ticks = 1) on that graph,
+ * with no graph in memory.  An agent left non-finite by a singular tick senses nobody and is sensed by nobody.
+ * SWARM_ERR_ARG (nothing written): a NULL ctx, sense_radius not positive and finite, non-finite dt /
+ * max_speed, negative ticks, overlapping or misaligned pos / pos_prev, non-finite positions at entry.
+ * All or nothing: when, at the start of some tick, the agents' 3 x 3 cell windows exceed swarm_build_rgg's
+ * work limits (2^36 candidate pairs, 2^20 in one window; judged on the device), the call returns
+ * SWARM_ERR_RANGE with *refused_tick (host, may be NULL; -1 otherwise) the absolute tick, and pos, pos_prev,
+ * vel, target, has_target, every array of fsm (both outbox halves) and counts hold exactly what they held at
+ * entry; no window of that tick or a later one was scanned.  To keep the progress up to a dense tick, run the
+ * loop in chunks.  Two host waits per call: the entry bounding box and the final verdict; none in the loop.
+ * The ctx keeps 114 bytes per agent for the entry state, next to the binning's scratch and the 16 bytes per
+ * agent of the cell-sorted snapshot.  n == 0 or ticks == 0: as swarm_update_loop.
+ */
+int swarm_update_loop_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                             const int32_t *row_ptr, const int32_t *col, const int32_t *hear_row_ptr,
+                             const int32_t *hear_col, const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0,
+                             int32_t ticks, double dt, double timeout, double jitter, uint64_t seed,
+                             const int64_t *kill_ticks, int32_t n_kill, double pull_frac, double *vel,
+                             double *target, uint8_t *has_target, int64_t m, const double *obstacles,
+                             double sense_radius, double max_speed, double *trace, int32_t trace_every,
+                             int64_t *counts, int64_t *n_singular, int64_t *refused_tick, void *stream);
 
 #ifdef __cplusplus
 }

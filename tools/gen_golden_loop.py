@@ -57,7 +57,9 @@ def make_loop_inputs(c):
                 radius=np.float64(RADIUS))
 
 
-def ref_loop(mod, inp):
+def ref_loop(mod, inp, sensed=None):
+    """sensed: None -- every tick's sensors are the agent's CSR row (U1); or a function of the tick's
+    snapshot returning every agent's sensed indices (U1-S, tools/gen_golden_loop_sensed.py)."""
     n = len(inp["ids"])
     ids, rp, col = inp["ids"], inp["row_ptr"], inp["col"]
     wide = int(ids.max()) > 255
@@ -110,9 +112,11 @@ def ref_loop(mod, inp):
             a.tick = t + int(inp["tick_off"][i])
             a._process_logic()
         snap = [(a.position[0], a.position[1]) for a in agents]
+        rows = sensed(snap) if sensed else None
         for i, a in enumerate(agents):
             if alive[i]:
-                a.update_sensors(obstacles, [(int(ids[j]), snap[j][0], snap[j][1]) for j in col[rp[i]:rp[i + 1]]])
+                a.update_sensors(obstacles, [(int(ids[j]), snap[j][0], snap[j][1])
+                                             for j in (rows[i] if sensed else col[rp[i]:rp[i + 1]])])
         for i, a in enumerate(agents):
             if alive[i]:
                 a._update_physics(dt)
