@@ -22,11 +22,16 @@ __device__ __forceinline__ int64_t cell_coord(double v, double vmin, double inv_
     return int64_t(f);
 }
 
+// fmin / fmax return the other operand for a NaN, so a NaN position leaves no trace in the box: the sensed
+// physics and loop rely on that (an agent a singular step left NaN is absent from every later step's grid).
+// kNanIsInf: a NaN coordinate counts as +inf instead, for the callers that refuse every non-finite position.
+template <bool kNanIsInf>
 static __global__ __launch_bounds__(kBlock) void k_bbox_partial(const double2 *__restrict__ pos,
                                                                int64_t n, double *__restrict__ part) {
     double mnx = DBL_MAX, mny = DBL_MAX, mxx = -DBL_MAX, mxy = -DBL_MAX;
     for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock) {
         const double2 p = pos[i];
+        if (kNanIsInf && (p.x != p.x || p.y != p.y)) mxx = HUGE_VAL;
         mnx = fmin(mnx, p.x); mny = fmin(mny, p.y);
         mxx = fmax(mxx, p.x); mxy = fmax(mxy, p.y);
     }
@@ -107,33 +112,31 @@ static __global__ __launch_bounds__(kBlock) void k_cell_offsets_search(const uin
     }
 }
 
-// Cells of side >= `cell` over g's bounding box (enlarged until the grid has at most max_cells).
-static inline void shape_grid(Grid *g, double cell, int64_t max_cells) {
-    double c = cell > 0 ? cell : 1.0;
-    for (;;) {
-        const double fx = std::floor((g->xmax - g->xmin) / c) + 1.0;
-        const double fy = std::floor((g->ymax - g->ymin) / c) + 1.0;
-        if (fx * fy <= double(max_cells)) {
-            g->ncx = int64_t(fx);
-            g->ncy = int64_t(fy);
-            break;
-        }
-        c *= 1.4142135623730951;
+// shape_grid (grid_shape.h) for a library entry point: a box without a finite extent is SWARM_ERR_ARG.
+static inline int shape_grid_checked(Grid *g, double cell, int64_t max_cells) {
+    if (!shape_grid(g, cell, max_cells)) {
+        set_error("invalid argument: %s", kExtentError);
+        return SWARM_ERR_ARG;
     }
-    g->cell = c;
-    g->inv_cell = 1.0 / c;
+    return SWARM_OK;
 }
 
 // Bounding box of n positions -> host Grid with cells of side >= `cell` (enlarged if the grid
-// would exceed max_cells).  One host sync (the grid shape sizes the launch).
+// would exceed max_cells).  One host sync (the grid shape sizes the launch).  SWARM_ERR_ARG for an
+// infinite position -- and for a NaN one with refuse_nan (k_bbox_partial) -- and for a box whose extent is
+// not finite.
 static inline int make_grid(swarm_ctx *ctx, int64_t n, const double *pos, double cell, int64_t max_cells,
-                            Grid *g, hipStream_t s) {
+                            Grid *g, hipStream_t s, bool refuse_nan = false) {
     const unsigned np = grid_for(n, kBlock, 1024);
     double *part;
     SW_ALLOC(part, ctx, S_BBOX, size_t(np) * 4 * 8 + 64);
     double *fin = part + size_t(np) * 4;
-    hipLaunchKernelGGL(k_bbox_partial, dim3(np), dim3(kBlock), 0, s,
-                       reinterpret_cast<const double2 *>(pos), n, part);
+    if (refuse_nan)
+        hipLaunchKernelGGL(k_bbox_partial<true>, dim3(np), dim3(kBlock), 0, s,
+                           reinterpret_cast<const double2 *>(pos), n, part);
+    else
+        hipLaunchKernelGGL(k_bbox_partial<false>, dim3(np), dim3(kBlock), 0, s,
+                           reinterpret_cast<const double2 *>(pos), n, part);
     SW_LAUNCHED();
     hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(64), 0, s, part, int(np), fin);
     SW_LAUNCHED();
@@ -146,8 +149,7 @@ static inline int make_grid(swarm_ctx *ctx, int64_t n, const double *pos, double
         return SWARM_ERR_ARG;
     }
     g->xmin = hb[0]; g->ymin = hb[1]; g->xmax = hb[2]; g->ymax = hb[3];
-    shape_grid(g, cell, max_cells);
-    return SWARM_OK;
+    return shape_grid_checked(g, cell, max_cells);
 }
 
 // Sort agents by cell.  On return *sorted_idx (device, n) lists agent indices cell by cell

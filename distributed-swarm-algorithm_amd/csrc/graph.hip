@@ -79,7 +79,7 @@ int swarm_build_rgg(swarm_ctx *ctx, int64_t n, const double *pos, double radius,
     }
     SW_ARG(pos != nullptr, "pos is NULL");
     Grid g;
-    int rc = make_grid(ctx, n, pos, radius * (1.0 + 1e-9), 4 * n + 1024, &g, s);
+    int rc = make_grid(ctx, n, pos, radius * (1.0 + 1e-9), 4 * n + 1024, &g, s, true);  // NaN positions refused
     if (rc) return rc;
     int32_t *sorted;
     uint32_t *off;
@@ -152,7 +152,7 @@ int swarm_cell_order(swarm_ctx *ctx, int64_t n, const double *pos, double cell, 
     SW_ARG(pos && perm, "NULL array");
     hipStream_t s = static_cast<hipStream_t>(stream);
     Grid g;
-    int rc = make_grid(ctx, n, pos, cell, 4 * n + 1024, &g, s);
+    int rc = make_grid(ctx, n, pos, cell, 4 * n + 1024, &g, s, true);  // NaN positions refused
     if (rc) return rc;
     int32_t *sorted;
     uint32_t *off;

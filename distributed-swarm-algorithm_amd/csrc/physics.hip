@@ -658,8 +658,7 @@ static int make_run_grid(swarm_ctx *ctx, int64_t n, const double *pos, double se
     g->ymin -= reach;
     g->xmax += reach;
     g->ymax += reach;
-    shape_grid(g, cell, max_cells);
-    return SWARM_OK;
+    return shape_grid_checked(g, cell, max_cells);  // the grown box's extent is checked again
 }
 
 int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t ticks, double dt,

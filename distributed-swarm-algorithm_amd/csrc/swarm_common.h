@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/swarm.h"
+#include "grid_shape.h"  // struct Grid (here so that headers without hipCUB can hold one) and its shaping
 
 namespace swarm {
 
@@ -19,13 +20,6 @@ constexpr int kWave = 64;
 constexpr int kElectCounters = 4;  // per-round election counters (elect.hip C_CHG..C_GHOST)
 
 void set_error(const char *fmt, ...);
-
-// A uniform grid of cells over a bounding box (binning.h; here so that headers without hipCUB can hold one).
-struct Grid {
-    double xmin, ymin, xmax, ymax;
-    double cell, inv_cell;
-    int64_t ncx, ncy;
-};
 
 // Scratch slots owned by a ctx; each grows on demand (never shrinks until destroy).
 enum Slot {

@@ -375,6 +375,9 @@ int swarm_utility(swarm_ctx *ctx, int64_t m, const double *apos, const uint32_t 
  * (device, capacity col_capacity) to fill.  SWARM_ERR_RANGE (before any row is built) when the
  * cell occupancies say the build would scan more than 2^36 candidate pairs in all or more than
  * 2^20 in one agent's 3 x 3 cell window (co-located agents), or the graph has >= 2^31 edges.
+ * SWARM_ERR_ARG (nothing written) for a position that is NaN or infinite, and for finite positions whose
+ * bounding box has no finite extent (max - min overflows a double); so does every call that grids positions
+ * (swarm_cell_order, swarm_cell_index, the sensed physics and loop, the auction) for such a box.
  */
 int swarm_build_rgg(swarm_ctx *ctx, int64_t n, const double *pos, double radius,
                     int32_t *row_ptr, int32_t *col, int64_t col_capacity, int64_t *n_edges,
@@ -382,7 +385,8 @@ int swarm_build_rgg(swarm_ctx *ctx, int64_t n, const double *pos, double radius,
 
 /*
  * Spatial storage order: perm (device, n) such that agents perm[0], perm[1], ... are
- * grouped by row-major grid cell of side `cell` (stable within a cell).
+ * grouped by row-major grid cell of side `cell` (stable within a cell).  SWARM_ERR_ARG for a position
+ * that is NaN or infinite.
  */
 int swarm_cell_order(swarm_ctx *ctx, int64_t n, const double *pos, double cell,
                      int32_t *perm, void *stream);
