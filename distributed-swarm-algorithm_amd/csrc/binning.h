@@ -15,13 +15,6 @@
 
 namespace swarm {
 
-__device__ __forceinline__ int64_t cell_coord(double v, double vmin, double inv_cell, int64_t nc) {
-    double f = floor((v - vmin) * inv_cell);
-    if (!(f >= 0.0)) return 0;            // also catches NaN
-    if (f >= double(nc - 1)) return nc - 1;
-    return int64_t(f);
-}
-
 // fmin / fmax return the other operand for a NaN, so a NaN position leaves no trace in the box: the sensed
 // physics and loop rely on that (an agent a singular step left NaN is absent from every later step's grid).
 // kNanIsInf: a NaN coordinate counts as +inf instead, for the callers that refuse every non-finite position.

@@ -62,9 +62,10 @@ struct LoopSense {
                               // work; [2], [3] that tick's candidate pairs (a double's bits), largest window
 };
 // The call's grid from the bounding box of `pos` (one host wait; non-finite positions: SWARM_ERR_ARG with
-// nothing written) and the verdict words cleared.
+// nothing written) and the verdict words cleared.  min_cell > 0: cells at least that wide (the radio loop
+// reads a second window, of that radius, on the same grid).
 int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t ticks, double dt,
-                     double max_speed, LoopSense *ls, hipStream_t s);
+                     double max_speed, LoopSense *ls, hipStream_t s, double min_cell = 0.0);
 // Tick k of the call (from 0), queued on `s`: the snapshot binned, its window work judged on the device
 // against swarm_build_rgg's limits, the cell-sorted copy of the snapshot.
 int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s);

@@ -646,9 +646,13 @@ int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const L
 // step, so the entry bounding box grown by the run's reach holds every finite position of every step
 // (cell_coord clamps the rest to an edge cell, which keeps two agents within R in adjacent cells).  One host
 // wait; non-finite positions are refused here, before anything is written.
+// min_cell: a second window read on the same grid (the radio loop's, of radius min_cell) needs its cells at
+// least that wide; the sensing predicate, not the cell, decides who is sensed, so wider cells only add
+// candidates.
 static int make_run_grid(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t steps,
-                         double dt, double max_speed, Grid *g, hipStream_t s) {
-    const double cell = (sense_radius < 2.0 ? sense_radius : 2.0) * (1.0 + 1e-9);
+                         double dt, double max_speed, Grid *g, hipStream_t s, double min_cell = 0.0) {
+    const double need = sense_radius < 2.0 ? sense_radius : 2.0;
+    const double cell = (need > min_cell ? need : min_cell) * (1.0 + 1e-9);
     const int64_t cap4 = 4 * n + 1024, max_cells = cap4 < (int64_t(1) << 31) ? cap4 : (int64_t(1) << 31);
     const int rc = make_grid(ctx, n, pos, cell, max_cells, g, s);
     if (rc) return rc;
@@ -662,8 +666,8 @@ static int make_run_grid(swarm_ctx *ctx, int64_t n, const double *pos, double se
 }
 
 int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t ticks, double dt,
-                     double max_speed, LoopSense *ls, hipStream_t s) {
-    const int rc = make_run_grid(ctx, n, pos, sense_radius, ticks, dt, max_speed, &ls->g, s);
+                     double max_speed, LoopSense *ls, hipStream_t s, double min_cell) {
+    const int rc = make_run_grid(ctx, n, pos, sense_radius, ticks, dt, max_speed, &ls->g, s, min_cell);
     if (rc) return rc;
     ls->r2 = sense_radius * sense_radius;
     ls->sorted = nullptr;

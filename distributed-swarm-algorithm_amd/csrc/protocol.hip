@@ -43,10 +43,14 @@
 // neighbours of every tick sensed from the tick's snapshot (physics.hip k_physics_loop_sensed): per tick the
 // snapshot is binned and its window work judged before the tick kernel, the tick kernels are untouched, and a
 // refused tick makes the call restore every caller array on the device (k_restore_refused: all or nothing).
+// swarm_update_loop_radio (contract U1-R) is the sensed loop without a message graph: the tick kernel
+// (k_tick_radio) is k_tick_pull's agent with the row walk replaced by the merge over the agent's 3 x 3 cell
+// window of the same binning, who hears whom judged on the tick's snapshot.
 #include <cmath>
 #include <cstring>
 
 #include "fsm_records.h"
+#include "window_merge.h"
 
 namespace swarm {
 namespace {
@@ -816,6 +820,7 @@ struct LoopArgs {
     int64_t *n_singular;  // host, may be NULL
     double sense_radius;  // > 0: contract U1-S, every tick senses its neighbours (sense_rp / sense_col unused)
     int64_t *refused_tick;  // U1-S; host, may be NULL
+    double radio_radius;    // > 0: contract U1-R, every tick senses who hears whom as well (no message graph)
 };
 
 // dst <- src (bytes) when a tick of the sensed loop was refused (st[0] != 0), else nothing: the entry
@@ -845,6 +850,161 @@ __global__ __launch_bounds__(kBlock) void k_swap_positions(int64_t n, double2 *_
     }
 }
 
+// ---------------------------------------------------------------- radio update loop (contract U1-R)
+// The tick's receive without a message graph: alive agent i hears j != i iff dx * dx + dy * dy <= r2 on the
+// tick's snapshot (swarm_build_rgg's rule), the heard senders' packets handled in ascending storage index (a
+// swarm_build_rgg row's order).  The snapshot's binning and cell-sorted copy are the sensed loop's
+// (loop_sense_tick); next to them a cell-sorted copy of the inbound outbox (1 byte per agent: a candidate
+// costs a streamed byte, not a gather) and one byte per cell, set when the cell holds a sender.
+struct Radio {
+    Grid g;
+    double r2;                         // radio_radius squared
+    const int32_t *sorted;             // the tick's binning (LoopSense)
+    const uint32_t *off;
+    const double2 *psort;
+    uint8_t *ob_sorted;                // ob_sorted[q] = ob_in[sorted[q]]
+    uint8_t *cell_send;                // [ncx * ncy], cleared per tick
+    const unsigned long long *st;      // the call's verdict word: != 0, a tick was refused
+};
+
+__global__ __launch_bounds__(kBlock) void k_radio_outbox(int64_t n, const uint8_t *__restrict__ ob_in, Radio w) {
+    if (w.st[0] != 0) return;
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n; q += int64_t(gridDim.x) * kBlock) {
+        const uint8_t o = ob_in[w.sorted[q]] & (kAcclaim | kHeartbeat);
+        w.ob_sorted[q] = o;
+        if (o) {  // (every writer of a cell's byte stores the same 1)
+            const double2 p = w.psort[q];
+            const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+            const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+            w.cell_send[cy * w.g.ncx + cx] = 1;
+        }
+    }
+}
+
+// k_tick_pull's agent over the window: threads in cell-sorted order (a wave's lanes share their windows and
+// the nine sender bytes; the records are gathered by storage index), the Rc predicate on the cell-sorted
+// snapshot, ids[j] gathered only for a candidate that sent and is in range.  Three ways through a tick, all
+// exact:
+//   skip    a receiver whose nine cells hold no sender hears nothing and runs only its timers;
+//   few     otherwise it scans the outbox bytes of the flagged cells only and keeps the heard senders' indices
+//           in a sorted register list of kHeardFast entries -- heartbeats come every tenth own tick from
+//           leaders only, so a window mostly holds one or two senders -- and handles them in ascending index;
+//   merge   when more senders are heard than the list holds, or more than kHeardCells of the nine cells hold
+//           senders (an election storm, a dense block), the window is walked by the nine-way merge of
+//           window_merge.h, every candidate in ascending index.
+// (The merge for every receiver with a flagged cell: 0.92 ms per tick at 10M agents against 0.64 in this form;
+// the list alone, a crowded window scanned first and merged after: 0.69.  DESIGN 4h.)
+// Returns at once when a tick of the call was refused (the caller restores every array).
+constexpr int kHeardFast = 4;
+constexpr int kHeardCells = 4;  // more window cells than this hold senders: no scan, the merge at once
+__global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, const int32_t *__restrict__ ids,
+                                                      const double2 *__restrict__ pos, Fsm f, Radio w,
+                                                      uint8_t *__restrict__ ob_out, double dt, double timeout,
+                                                      double jitter, uint64_t seed,
+                                                      unsigned long long *__restrict__ counts) {
+    __shared__ unsigned s_cnt[4];
+    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const double now = double(t) * dt;
+    unsigned c_lead = 0, c_wait = 0, c_acc = 0, c_hb = 0;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const int64_t i = w.sorted[q0];
+        const uint2 r = f.rec[i];
+        const uint32_t fw = r.x;
+        if (!fw_alive(fw)) {
+            ob_out[i] = 0;
+            continue;
+        }
+        const double2 p = w.psort[q0];
+        const int32_t me = ids[i];
+        const uint8_t st0 = fw_state(fw);
+        const int32_t ph = fw_phase(fw);
+        const bool hb_tick = ((t + ph) % 10) == 0;
+        uint32_t bits = fw_bits(fw);
+        int32_t y = int32_t(r.y);
+        Heard h{st0, 0, false, false, 0, -1};
+        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+        unsigned cells = 0;  // bit k: window cell k holds a sender (the nine bytes loaded at once)
+        uint8_t flag[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int64_t yy = cy + (k / 3) - 1, xx = cx + (k % 3) - 1;
+            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
+            flag[k] = w.cell_send[in ? yy * w.g.ncx + xx : 0];
+            cells |= in ? 1u << k : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) cells &= flag[k] ? ~0u : ~(1u << k);
+        // senders all around (an election storm): the list would overflow, merge at once
+        const bool crowded = __popc(cells) > kHeardCells;
+        if (cells) {
+            // the heard senders of the flagged cells, the kHeardFast lowest indices kept in ascending order
+            // (an insertion network on registers); one more than fit: the window is merged instead
+            int32_t sj[kHeardFast];
+            uint8_t so[kHeardFast];
+#pragma unroll
+            for (int u = 0; u < kHeardFast; ++u) {
+                sj[u] = kMergeEnd;
+                so[u] = 0;
+            }
+            bool more = crowded;
+            for (int k = 0; k < 9 && !crowded; ++k) {
+                if (!((cells >> k) & 1u)) continue;
+                const int64_t c = (cy + (k / 3) - 1) * w.g.ncx + cx + (k % 3) - 1;
+                for (uint32_t q = w.off[c], e = w.off[c + 1]; q < e; ++q) {
+                    uint8_t o = w.ob_sorted[q];
+                    if (!o) continue;
+                    int32_t j = w.sorted[q];
+                    const double2 s = w.psort[q];
+                    const double ex = p.x - s.x, ey = p.y - s.y;
+                    if (j == int32_t(i) || !(ex * ex + ey * ey <= w.r2)) continue;
+#pragma unroll
+                    for (int u = 0; u < kHeardFast; ++u) {
+                        const bool lower = j < sj[u];
+                        const int32_t tj = sj[u];
+                        const uint8_t to = so[u];
+                        sj[u] = lower ? j : tj;
+                        so[u] = lower ? o : to;
+                        j = lower ? tj : j;
+                        o = lower ? to : o;
+                    }
+                    more |= j != kMergeEnd;  // an index fell off the end of the list
+                }
+            }
+            if (!more) {
+                int32_t ss[kHeardFast];  // the senders' IDs, all loads in flight
+#pragma unroll
+                for (int u = 0; u < kHeardFast; ++u) ss[u] = sj[u] != kMergeEnd ? ids[sj[u]] : 0;
+#pragma unroll
+                for (int u = 0; u < kHeardFast; ++u)
+                    if (sj[u] != kMergeEnd) hear(h, so[u], ss[u], sj[u], me, hb_tick);
+            } else {
+                window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
+                    const uint8_t o = w.ob_sorted[q];
+                    if (!o || j == int32_t(i)) return;
+                    const double2 s = w.psort[q];
+                    const double ex = p.x - s.x, ey = p.y - s.y;
+                    if (ex * ex + ey * ey <= w.r2) hear(h, o, ids[j], j, me, hb_tick);
+                });
+            }
+        }
+        apply_heard(i, h, t, pos, f, bits, y);
+        const uint8_t ob = h.ob | timers(i, h.st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
+                                         ph, f, bits, y);
+        const uint32_t fw1 = fw_make(h.st, 1, bits, ph);
+        if (fw1 != fw || uint32_t(y) != r.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
+        if (h.lead_set) f.lrec[i].leader = h.lead;
+        ob_out[i] = ob;
+        c_lead += h.st == ST_L;
+        c_wait += h.st == ST_W;
+        c_acc += (ob & kAcclaim) != 0;
+        c_hb += (ob & kHeartbeat) != 0;
+    }
+    add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
+}
+
 // The ticks t0+1 .. t0+ticks of swarm_protocol_run_ex, and of swarm_update_loop when `loop` is given (each
 // tick then followed by its physics step; `pos` is not used, the heartbeats read the lagged buffer).
 int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
@@ -857,7 +1017,8 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
     SW_ARG(n_kill == 0 || kill_ticks != nullptr, "kill_ticks is NULL");
     SW_ARG(std::isfinite(dt) && timeout >= 0.0 && jitter >= 0.0, "dt / timeout / jitter out of range");
     SW_ARG(hear_row_ptr != nullptr || hear_col == nullptr, "hear_col without hear_row_ptr");
-    SW_ARG(n == 0 || (ids && pos && row_ptr && tick_off && fsm->state && fsm->leader && fsm->last_hb &&
+    const bool radio = loop && loop->radio_radius > 0.0;
+    SW_ARG(n == 0 || (ids && pos && (row_ptr || radio) && tick_off && fsm->state && fsm->leader && fsm->last_hb &&
                       fsm->wait_start && fsm->delay && fsm->leader_pos && fsm->has_leader_pos && fsm->alive &&
                       fsm->outbox),
            "NULL agent array");
@@ -880,7 +1041,9 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
     int n_kept = 0;
     uint8_t *snap = nullptr;
     if (sensed) {
-        const int rc = loop_sense_begin(ctx, n, loop->pos, loop->sense_radius, ticks, dt, loop->max_speed, &ls, s);
+        // (U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
+        const int rc = loop_sense_begin(ctx, n, loop->pos, loop->sense_radius, ticks, dt, loop->max_speed, &ls, s,
+                                        radio ? loop->radio_radius : 0.0);
         if (rc) return rc;
         const size_t un = size_t(n);
         const Kept all[14] = {{loop->pos, un * 16, 0},       {loop->pos_prev, un * 16, 0},  {loop->vel, un * 16, 0},
@@ -1010,6 +1173,14 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
     }
     SW_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tick_clk), &clk_buf, sizeof(clk_buf), 0, hipMemcpyHostToDevice, s));
 #endif
+    Radio rw{};
+    if (radio) {  // no mail bitmap, no sender segments: the receivers find their senders in their windows
+        rw.g = ls.g;
+        rw.r2 = loop->radio_radius * loop->radio_radius;
+        rw.st = ls.st;
+        SW_ALLOC(rw.ob_sorted, ctx, S_RADIO_OUTBOX, size_t(n));
+        SW_ALLOC(rw.cell_send, ctx, S_RADIO_CELLS, size_t(ls.g.ncx * ls.g.ncy));
+    }
     double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
     for (int64_t t = t0 + 1; t <= t0 + ticks; ++t) {
         if (loop) pos = lag;  // a heartbeat sent during tick t-1 carries its sender's position of then
@@ -1026,7 +1197,17 @@ int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, 
         const uint8_t *ob_in = fsm->outbox + size_t((t - 1) & 1) * size_t(n);
         uint8_t *ob_out = fsm->outbox + size_t(t & 1) * size_t(n);
         unsigned long long *cnt = d_cnt + size_t(t - t0 - 1) * kShards * 4;
-        if (push) {
+        if (radio) {
+            rw.sorted = ls.sorted;
+            rw.off = ls.off;
+            rw.psort = ls.psort;
+            SW_HIP(hipMemsetAsync(rw.cell_send, 0, size_t(ls.g.ncx * ls.g.ncy), s));
+            hipLaunchKernelGGL(k_radio_outbox, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ob_in, rw);
+            SW_LAUNCHED();
+            hipLaunchKernelGGL(k_tick_radio, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, t, ids,
+                               reinterpret_cast<const double2 *>(pos), f, rw, ob_out, dt, timeout, jitter, seed,
+                               cnt);
+        } else if (push) {
             NextMail im{};
             im.next = mail_of(t + 1);
             im.clear = mail_of(t + 2).bits;
@@ -1221,6 +1402,36 @@ int swarm_update_loop_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, doub
                         trace, trace_every, n_singular, sense_radius, refused_tick};
     return run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt, timeout,
                      jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream);
+}
+
+int swarm_update_loop_radio(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                            const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                            double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                            int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                            const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                            double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                            int64_t *refused_tick, void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(n >= 0 && n < (int64_t(1) << 31) - 1 && m >= 0 && ticks >= 0, "sizes out of range");
+    SW_ARG(radio_radius > 0 && std::isfinite(radio_radius), "radio_radius must be positive and finite");
+    SW_ARG(sense_radius > 0 && std::isfinite(sense_radius), "sense_radius must be positive and finite");
+    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
+    SW_ARG(n == 0 || (pos && pos_prev && vel && target && has_target), "NULL agent array");
+    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
+    SW_ARG(trace_every >= 0, "trace_every must not be negative");
+    SW_ARG(n == 0 || trace_every == 0 || ticks / trace_every == 0 || trace != nullptr, "trace is NULL");
+    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
+        const uintptr_t a = reinterpret_cast<uintptr_t>(pos), b = reinterpret_cast<uintptr_t>(pos_prev);
+        SW_ARG((a > b ? a - b : b - a) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
+        SW_ARG((a & 15) == 0 && (b & 15) == 0, "pos / pos_prev are not 16-byte aligned");
+    }
+    if (n_singular) *n_singular = 0;
+    if (refused_tick) *refused_tick = -1;
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
+                        trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
+    return run_ticks(ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt, timeout,
+                     jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream);
 }
 
 }  // extern "C"

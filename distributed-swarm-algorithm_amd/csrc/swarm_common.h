@@ -62,6 +62,8 @@ enum Slot {
     S_SENSE_SORTED,   // sensed physics: the step's positions in cell-sorted order
     S_SENSE_STATE,    // sensed physics: stop word, singular count and the refused step's window figures
     S_LOOP_SNAP,      // sensed update loop: the caller's arrays as they were at entry (restored on a refusal)
+    S_RADIO_OUTBOX,   // radio update loop: the tick's inbound outbox bytes in cell-sorted order
+    S_RADIO_CELLS,    // radio update loop: one byte per grid cell, set when the cell holds a sender
     S_NUM
 };
 
@@ -204,6 +206,15 @@ inline unsigned grid_for(int64_t work, int64_t per_block, unsigned cap = 8192) {
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return static_cast<unsigned>(g);
+}
+
+// The cell of coordinate v on one axis of a Grid (binning.h bins by it; here so that a kernel that only reads
+// a binning needs no hipCUB).
+__device__ __forceinline__ int64_t cell_coord(double v, double vmin, double inv_cell, int64_t nc) {
+    double f = floor((v - vmin) * inv_cell);
+    if (!(f >= 0.0)) return 0;            // also catches NaN
+    if (f >= double(nc - 1)) return nc - 1;
+    return int64_t(f);
 }
 
 }  // namespace swarm

@@ -1,0 +1,59 @@
+// The streaming nine-way merge over an agent's 3 x 3 cell window (physics.hip k_physics_sensed describes
+// it), as a function over "candidate (j, q)": storage index j at cell-sorted position q, visited in ascending
+// j -- the agent itself included, the caller's predicate decides the rest.  A window is up to nine runs of
+// sorted_idx, one per cell, each ascending (the binning's sort is stable): nine cursors, ends and head
+// indices in registers, the smallest head taken each turn; no list, no capacity, no fallback.
+// k_physics_sensed and window_separation (physics.hip) keep their own written-out copies of these
+// statements: their machine code is what S1's and U1-S's figures were measured on.  New
+// walkers go through this one.
+#pragma once
+
+#include "swarm_common.h"
+
+namespace swarm {
+
+constexpr int32_t kMergeEnd = 0x7fffffff;  // no head: the run is exhausted (n < 2^31 - 1)
+
+template <class Visit>
+__device__ __forceinline__ void window_merge(double px, double py, const Grid &g,
+                                             const int32_t *__restrict__ sorted_idx,
+                                             const uint32_t *__restrict__ off, Visit &&visit) {
+    const int64_t cx = cell_coord(px, g.xmin, g.inv_cell, g.ncx);
+    const int64_t cy = cell_coord(py, g.ymin, g.inv_cell, g.ncy);
+    uint32_t cur[9], end[9];
+    int32_t head[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int64_t yy = cy + (k / 3) - 1, xx = cx + (k % 3) - 1;
+        const bool in = yy >= 0 && yy < g.ncy && xx >= 0 && xx < g.ncx;
+        const int64_t c = in ? yy * g.ncx + xx : 0;
+        cur[k] = in ? off[c] : 0u;
+        end[k] = in ? off[c + 1] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kMergeEnd;
+    for (;;) {
+        int32_t j = head[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) j = head[k] < j ? head[k] : j;
+        if (j == kMergeEnd) break;
+        uint32_t q = 0, e = 0;  // the run that holds j (indices are distinct: exactly one)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const bool hit = head[k] == j;
+            q = hit ? cur[k] : q;
+            e = hit ? end[k] : e;
+        }
+        const uint32_t qn = q + 1;
+        const int32_t hn = qn < e ? sorted_idx[qn] : kMergeEnd;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const bool hit = head[k] == j;
+            cur[k] = hit ? qn : cur[k];
+            head[k] = hit ? hn : head[k];
+        }
+        visit(j, q);
+    }
+}
+
+}  // namespace swarm

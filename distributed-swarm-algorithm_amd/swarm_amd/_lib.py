@@ -38,7 +38,7 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_comm_unique_id_kind", "swarm_comm_create_kind", "swarm_comm_kind", "swarm_allocate_indexed_ex",
            "swarm_protocol_run_ex", "swarm_elect_sharded_ex", "swarm_graph_compact_escaped",
            "swarm_frontier_set_compact_escaped", "swarm_physics_run_sensed", "swarm_update_loop",
-           "swarm_update_loop_sensed")
+           "swarm_update_loop_sensed", "swarm_update_loop_radio")
 
 
 class SwarmError(RuntimeError):
@@ -173,6 +173,9 @@ def load(path: str = LIB_PATH):
         L.swarm_update_loop_sensed.argtypes = [P, i64, P, P, P, P, P, P, P, P, ctypes.POINTER(Fsm), i64, i32, d, d, d,
                                                ctypes.c_uint64, P, i32, d, P, P, P, i64, P, d, d, P, i32, P,
                                                ctypes.POINTER(i64), ctypes.POINTER(i64), P]
+        L.swarm_update_loop_radio.argtypes = [P, i64, P, P, P, P, ctypes.POINTER(Fsm), i64, i32, d, d, d,
+                                              ctypes.c_uint64, P, i32, P, P, P, i64, P, d, d, d, P, i32, P,
+                                              ctypes.POINTER(i64), ctypes.POINTER(i64), P]
         L.swarm_auction_begin.argtypes = [P, i64, P, P, P, i64, P, P, d, d, ctypes.c_float, P, P, P, P, P]
         L.swarm_auction_bid.argtypes = [P, i64, i32, i32, P, P, P, P]
         L.swarm_auction_resolve.argtypes = [P, i64, i32, P, P, P, P, P, P]

@@ -778,9 +778,31 @@ class Swarm:
         return self._update_loop(ticks, float(sense_radius), obstacles, None, kill_ticks, dt, timeout, jitter, seed,
                                  max_speed, mode, pull_frac, trace_every)
 
+    def update_loop_radio(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
+                          kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
+                          max_speed: float = 5.0, trace_every: int = 0) -> dict:
+        """update_loop_sensed with who hears whom re-sensed every tick as well (contract U1-R;
+        swarm_update_loop_radio): at tick t an alive agent hears every other agent within radio_radius of it in
+        the positions at the start of the tick -- the snapshot the tick's sensors read -- and receives what
+        those sent during tick t-1 in ascending storage index; a heartbeat still carries the position its
+        sender packed a tick earlier.  An agent that has moved out of its leader's range stops hearing it,
+        times out and re-elects.  The result of "radius graph of the current storage positions at
+        radio_radius as the message graph, then update_loop_sensed(1, sense_radius)" repeated, bit for bit,
+        with no graph built: the swarm needs no neighbour graph, and self.row_ptr / self.col are untouched
+        when it has one.  Keywords, self.fsm / self.fsm_tick / self.pos_prev, the returned dict, the
+        all-or-nothing refusal of a too-dense tick and self.last_refused_tick as update_loop_sensed; the calls
+        of the three loops chain into one run."""
+        radio_radius, sense_radius = float(radio_radius), float(sense_radius)
+        for name, r in (("radio_radius", radio_radius), ("sense_radius", sense_radius)):
+            if not (r > 0.0 and np.isfinite(r)):
+                raise ValueError(f"{name} must be positive and finite, got {r}")
+        return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
+                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius)
+
     def _update_loop(self, ticks, sense_radius, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed,
-                     max_speed, mode, pull_frac, trace_every) -> dict:
-        """update_loop (sense_radius None: the `sensors` lists, fixed) and update_loop_sensed."""
+                     max_speed, mode, pull_frac, trace_every, radio_radius=None) -> dict:
+        """update_loop (sense_radius None: the `sensors` lists, fixed), update_loop_sensed and
+        update_loop_radio (radio_radius given: no message graph)."""
         ticks, trace_every = int(ticks), int(trace_every)
         if mode not in ("push", "pull", "hybrid"):
             raise ValueError(f"unknown mode {mode!r}")
@@ -788,7 +810,7 @@ class Swarm:
             raise ValueError("ticks must not be negative")
         if trace_every < 0:
             raise ValueError("trace_every must not be negative")
-        if self.row_ptr is None:
+        if self.row_ptr is None and radio_radius is None:
             raise RuntimeError("no neighbour graph: call build_graph() or set_graph()")
         dev, n = self.device, self.n
         if not hasattr(self, "fsm"):
@@ -809,9 +831,10 @@ class Swarm:
                         (self.state, self.leader, f["last_hb"], f["wait_start"], f["delay"], f["leader_pos"],
                          f["has_leader_pos"], f["alive"], f["outbox"])])
         kt = np.ascontiguousarray(np.asarray(kill_ticks, np.int64))
-        h = getattr(self, "_hear", None) or (self.row_ptr, self.col)
-        hear = (None, None) if mode == "pull" or n == 0 else \
-            (_lib.ptr(h[0], torch.int32), _lib.ptr(h[1], torch.int32) if h[1].numel() else None)
+        if radio_radius is None:
+            h = getattr(self, "_hear", None) or (self.row_ptr, self.col)
+            hear = (None, None) if mode == "pull" or n == 0 else \
+                (_lib.ptr(h[0], torch.int32), _lib.ptr(h[1], torch.int32) if h[1].numel() else None)
         counts = np.zeros((ticks, 4), np.int64)
         frames = ticks // trace_every if trace_every else 0
         trace = torch.empty((frames, n, 2), dtype=torch.float64, device=dev) if trace_every else None
@@ -819,15 +842,21 @@ class Swarm:
         p = lambda t: _lib.ptr(t) if n else None  # noqa: E731
         refused = ctypes.c_int64(-1)
         with torch.cuda.device(dev):
-            head = (_lib.ctx(), n, p(self.ids), p(self.pos), p(self.pos_prev), _lib.ptr(self.row_ptr, torch.int32),
-                    _lib.ptr(self.col, torch.int32) if self.n_edges else None, *hear, p(self.tick_off),
-                    ctypes.byref(fs), self.fsm_tick, ticks, float(dt), float(timeout), float(jitter),
-                    ctypes.c_uint64(int(seed)), kt.ctypes.data_as(ctypes.c_void_p) if kt.size else None, kt.size,
-                    float(pull_frac) if mode == "hybrid" else -1.0, p(self.vel), p(self.target),
-                    p(self.has_target), obs.shape[0], _lib.ptr(obs) if obs.numel() else None)
+            graph = () if radio_radius is not None else \
+                (_lib.ptr(self.row_ptr, torch.int32), _lib.ptr(self.col, torch.int32) if self.n_edges else None, *hear)
+            run = (p(self.tick_off), ctypes.byref(fs), self.fsm_tick, ticks, float(dt), float(timeout), float(jitter),
+                   ctypes.c_uint64(int(seed)), kt.ctypes.data_as(ctypes.c_void_p) if kt.size else None, kt.size)
+            motion = (p(self.vel), p(self.target), p(self.has_target), obs.shape[0],
+                      _lib.ptr(obs) if obs.numel() else None)
+            head = (_lib.ctx(), n, p(self.ids), p(self.pos), p(self.pos_prev), *graph, *run,
+                    *(() if radio_radius is not None else (float(pull_frac) if mode == "hybrid" else -1.0,)), *motion)
             tail = (float(max_speed), _lib.ptr(trace) if frames and n else None, trace_every,
                     counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(sing))
-            if sense_radius is None:
+            if radio_radius is not None:
+                rc = _lib.lib().swarm_update_loop_radio(*head, float(radio_radius), float(sense_radius), *tail,
+                                                        ctypes.byref(refused), _lib.stream())
+                self.last_refused_tick = refused.value
+            elif sense_radius is None:
                 rc = _lib.lib().swarm_update_loop(
                     *head, _lib.ptr(srp, torch.int32), _lib.ptr(scol, torch.int32) if scol.numel() else None,
                     *tail, _lib.stream())

@@ -654,6 +654,37 @@ int swarm_update_loop_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, doub
                              double sense_radius, double max_speed, double *trace, int32_t trace_every,
                              int64_t *counts, int64_t *n_singular, int64_t *refused_tick, void *stream);
 
+/*
+ * swarm_update_loop_sensed with the radio neighbours re-sensed as well (contract U1-R): there is no message
+ * graph.  Tick t, with S = P_{t-1} the snapshot its sensors read: alive agent i hears agent j != i iff
+ * dx*dx + dy*dy <= radio_radius^2 on S (fp64, the products rounded separately, radio_radius^2 computed once:
+ * swarm_build_rgg's rule) and receives what each heard j sent during tick t-1 in ascending storage index (a
+ * swarm_build_rgg row's order; the handlers are order-dependent: a follower's leader and leader_pos are the
+ * last heartbeat's in that order).  A heartbeat still carries its sender's f32-rounded P_{t-2}: who hears is
+ * judged on P_{t-1}, what is heard was packed a tick earlier.  Dead agents neither send nor receive and are
+ * still sensed as bodies at rest; an agent left non-finite by a singular tick hears nobody and is heard by
+ * nobody.  Everything else -- kills, timers, the sensed physics at sense_radius, pos / pos_prev, trace,
+ * counts, n_singular -- is swarm_update_loop_sensed's, argument for argument.  The state after the call is
+ * bit-identical to `ticks` repetitions of swarm_build_rgg(pos, radio_radius) as the message graph +
+ * swarm_update_loop_sensed(ticks = 1, sense_radius) (finite positions: swarm_build_rgg refuses a NaN), with
+ * no graph in memory; calls chain with swarm_update_loop / swarm_update_loop_sensed through fsm, t0 and
+ * pos_prev.
+ * SWARM_ERR_ARG (nothing written): either radius not positive and finite, and whatever
+ * swarm_update_loop_sensed refuses.  All or nothing as swarm_update_loop_sensed: both windows are read on one
+ * grid per call, of cells max(radio_radius, min(sense_radius, 2)) wide, and its window work is judged on the
+ * device at the start of every tick; a refused tick returns SWARM_ERR_RANGE with *refused_tick set and every
+ * caller array as it was at entry.  Two host waits per call: the entry bounding box and the final verdict.
+ * The ctx keeps, next to swarm_update_loop_sensed's scratch, one byte per agent (the cell-sorted outbox) and
+ * one per grid cell (the cells that hold a sender).  n == 0 or ticks == 0: as swarm_update_loop.
+ */
+int swarm_update_loop_radio(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                            const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                            double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                            int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                            const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                            double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                            int64_t *refused_tick, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,9 +57,12 @@ def make_loop_inputs(c):
                 radius=np.float64(RADIUS))
 
 
-def ref_loop(mod, inp, sensed=None):
+def ref_loop(mod, inp, sensed=None, heard=None):
     """sensed: None -- every tick's sensors are the agent's CSR row (U1); or a function of the tick's
-    snapshot returning every agent's sensed indices (U1-S, tools/gen_golden_loop_sensed.py)."""
+    snapshot returning every agent's sensed indices (U1-S, tools/gen_golden_loop_sensed.py).
+    heard: None -- every tick's packets come along the agent's CSR row; or a function of the snapshot at the
+    start of the tick (before the receive phase) returning every agent's heard indices in ascending order,
+    dead agents included (U1-R, tools/gen_golden_loop_radio.py): the delivery loop iterates those."""
     n = len(inp["ids"])
     ids, rp, col = inp["ids"], inp["row_ptr"], inp["col"]
     wide = int(ids.max()) > 255
@@ -92,12 +95,13 @@ def ref_loop(mod, inp, sensed=None):
             for i, a in enumerate(agents):
                 if alive[i] and a.state == L:
                     alive[i] = False
+        hears = heard([(a.position[0], a.position[1]) for a in agents]) if heard else None
         for i, a in enumerate(agents):
             if not alive[i]:
                 continue
             a.tick = t + int(inp["tick_off"][i])
-            for k in range(rp[i], rp[i + 1]):
-                for pkt in out_prev[col[k]]:
+            for j in (hears[i] if heard else col[rp[i]:rp[i + 1]]):
+                for pkt in out_prev[j]:
                     if wide:  # on_message_received slices a 6-byte header: dispatch as it does
                         mt, snd, _ = struct.unpack("!BII", pkt[:9])
                         pl = pkt[9:]
