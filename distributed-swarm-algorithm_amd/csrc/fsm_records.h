@@ -67,11 +67,14 @@ struct LoopSense {
 int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t ticks, double dt,
                      double max_speed, LoopSense *ls, hipStream_t s, double min_cell = 0.0);
 // Tick k of the call (from 0), queued on `s`: the snapshot binned, its window work judged on the device
-// against swarm_build_rgg's limits, the cell-sorted copy of the snapshot.
-int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s);
-// The error of a call whose verdict words h (st read back) report a refused tick: "too dense", the absolute
-// tick and the window figures; returns SWARM_ERR_RANGE.
-int loop_sense_refusal(const unsigned long long *h, int64_t tick);
+// against swarm_build_rgg's limits, the cell-sorted copy of the snapshot.  offsets_by_search: the cells'
+// offsets by search (bin_agents' sparse_grid) -- the loops' grid reaches far beyond the agents, by the run's
+// reach on every side; swarm_physics_run_sensed keeps the dense form its figures were measured on.
+int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s,
+                    bool offsets_by_search);
+// The error of a call whose verdict words h (st read back) report a refused tick: the caller's wording
+// (printf-style: "too dense ... at tick / step ..."), then the window figures; returns SWARM_ERR_RANGE.
+int loop_sense_refusal(const unsigned long long *h, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 // launch_physics_loop with the row of a sensor CSR replaced by the agent's 3 x 3 cell window of
 // loop_sense_tick's binning (the snapshot is read through ls.psort); does nothing once a tick was refused.
 int launch_physics_loop_sensed(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, double *pos_out,

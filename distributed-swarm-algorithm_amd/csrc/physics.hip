@@ -24,8 +24,11 @@
 // directly -- no degree pass, no scan, no CSR in memory.
 #include <cmath>
 
+#include <cstdarg>
+
 #include "binning.h"
 #include "fsm_records.h"
+#include "window_merge.h"
 
 namespace swarm {
 namespace {
@@ -204,7 +207,9 @@ __device__ __forceinline__ void count_singular(unsigned long long sing, unsigned
 
 // k_physics keeps its body written out and shares only the separation term: routed through the helpers
 // above (formation_target, obstacle_forces, attraction, integrate) the compiler laid its blocks out
-// differently and the f1 step measured 1-2 % slower; in this form its machine code is what it was.
+// differently and the f1 step measured 1-2 % slower; in this form its machine code is what it was.  (Its row
+// walk and k_physics_loop's as one function returning a SepAcc: 1 680 / 1 682 instructions for 1 681 / 1 683,
+// not the same streams -- both keep the walk written out.)
 __global__ __launch_bounds__(kBlock, 8) void k_physics(int64_t n, const int32_t *__restrict__ ids,
                                                    const uint8_t *__restrict__ state,
                                                    const int32_t *__restrict__ leader,
@@ -411,8 +416,7 @@ __global__ __launch_bounds__(kBlock, 8) void k_physics_loop(
 // index, not gathered.  Cells of side >= min(R, 2) (1 + 1e-9) suffice: a neighbour farther than 2.0
 // adds no term.  A non-finite agent sits in an edge cell (cell_coord), fails every <= and so senses
 // nobody and is sensed by nobody.  st[0] != 0 (a step refused for its window work): the step only
-// copies the positions through.
-constexpr int32_t kNoHead = 0x7fffffff;
+// copies the positions through.  (kMergeEnd, window_merge.h: the head of an exhausted run.)
 
 __global__ __launch_bounds__(kBlock) void k_sorted_positions(const double2 *__restrict__ pin, int64_t n,
                                                             const int32_t *__restrict__ sorted_idx,
@@ -479,7 +483,7 @@ __global__ __launch_bounds__(kBlock) void k_physics_sensed(
             end[k] = in ? off[c + 1] : 0u;
         }
 #pragma unroll
-        for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kNoHead;
+        for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kMergeEnd;
         double fax = 0.0, fay = 0.0;
         attraction(px, py, t, fax, fay);
         double fsx = 0.0, fsy = 0.0;
@@ -487,7 +491,7 @@ __global__ __launch_bounds__(kBlock) void k_physics_sensed(
             int32_t j = head[0];
 #pragma unroll
             for (int k = 1; k < 9; ++k) j = head[k] < j ? head[k] : j;
-            if (j == kNoHead) break;
+            if (j == kMergeEnd) break;
             uint32_t q = 0, e = 0;  // the run that holds j (indices are distinct: exactly one)
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
@@ -497,7 +501,7 @@ __global__ __launch_bounds__(kBlock) void k_physics_sensed(
             }
             const double2 o = psort[q];
             const uint32_t qn = q + 1;
-            const int32_t hn = qn < e ? sorted_idx[qn] : kNoHead;
+            const int32_t hn = qn < e ? sorted_idx[qn] : kMergeEnd;
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
                 const bool hit = head[k] == j;
@@ -526,7 +530,8 @@ __global__ __launch_bounds__(kBlock) void k_physics_sensed(
 // statements on the same operands, hence the same bits.  (k_physics_sensed keeps its body written out:
 // routed through this function, whole or split into the window's opening and its merge, the compiler
 // scheduled it differently -- 1 155 / 1 160 instructions for 1 165 -- and S1's figures were measured on
-// the form it has.)
+// the form it has.  This function through window_merge (window_merge.h) with a visiting lambda was compiled
+// too: k_physics_loop_sensed 1 141 instructions for 1 169, so it keeps the statements as well.)
 __device__ __forceinline__ SepAcc window_separation(int64_t i, double px, double py, const Grid &g, double r2,
                                                     const int32_t *__restrict__ sorted_idx,
                                                     const uint32_t *__restrict__ off,
@@ -544,13 +549,13 @@ __device__ __forceinline__ SepAcc window_separation(int64_t i, double px, double
         end[k] = in ? off[c + 1] : 0u;
     }
 #pragma unroll
-    for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kNoHead;
+    for (int k = 0; k < 9; ++k) head[k] = cur[k] < end[k] ? sorted_idx[cur[k]] : kMergeEnd;
     double fsx = 0.0, fsy = 0.0;
     for (;;) {
         int32_t j = head[0];
 #pragma unroll
         for (int k = 1; k < 9; ++k) j = head[k] < j ? head[k] : j;
-        if (j == kNoHead) break;
+        if (j == kMergeEnd) break;
         uint32_t q = 0, e = 0;  // the run that holds j (indices are distinct: exactly one)
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
@@ -560,7 +565,7 @@ __device__ __forceinline__ SepAcc window_separation(int64_t i, double px, double
         }
         const double2 o = psort[q];
         const uint32_t qn = q + 1;
-        const int32_t hn = qn < e ? sorted_idx[qn] : kNoHead;
+        const int32_t hn = qn < e ? sorted_idx[qn] : kMergeEnd;
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const bool hit = head[k] == j;
@@ -650,7 +655,7 @@ int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const L
 // least that wide; the sensing predicate, not the cell, decides who is sensed, so wider cells only add
 // candidates.
 static int make_run_grid(swarm_ctx *ctx, int64_t n, const double *pos, double sense_radius, int32_t steps,
-                         double dt, double max_speed, Grid *g, hipStream_t s, double min_cell = 0.0) {
+                         double dt, double max_speed, Grid *g, hipStream_t s, double min_cell) {
     const double need = sense_radius < 2.0 ? sense_radius : 2.0;
     const double cell = (need > min_cell ? need : min_cell) * (1.0 + 1e-9);
     const int64_t cap4 = 4 * n + 1024, max_cells = cap4 < (int64_t(1) << 31) ? cap4 : (int64_t(1) << 31);
@@ -678,11 +683,12 @@ int loop_sense_begin(swarm_ctx *ctx, int64_t n, const double *pos, double sense_
     return SWARM_OK;
 }
 
-int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s) {
+int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, LoopSense *ls, hipStream_t s,
+                    bool offsets_by_search) {
     double *acc;
     int rc;
-    // the call's grid reaches far beyond the agents (the run's reach on every side): offsets by search
-    if ((rc = bin_agents(ctx, n, pos_in, ls->g, &ls->sorted, &ls->off, s, true))) return rc;
+    if ((rc = bin_agents(ctx, n, pos_in, ls->g, &ls->sorted, &ls->off, s, offsets_by_search))) return rc;
+    // the window work against swarm_build_rgg's limits, judged on the device: a refused tick sets the stop word
     if ((rc = launch_window_work(ctx, ls->off, ls->g, s, &acc))) return rc;
     hipLaunchKernelGGL(k_sense_verdict, dim3(1), dim3(1), 0, s, acc, ls->st, k);
     SW_LAUNCHED();
@@ -692,12 +698,14 @@ int loop_sense_tick(swarm_ctx *ctx, int64_t n, const double *pos_in, int32_t k, 
     return SWARM_OK;
 }
 
-int loop_sense_refusal(const unsigned long long *h, int64_t tick) {
+int loop_sense_refusal(const unsigned long long *h, const char *fmt, ...) {
     double pairs;
     memcpy(&pairs, h + 2, 8);
     char what[112];
-    snprintf(what, sizeof(what), "agents too dense to sense at tick %lld (nothing of the call is kept)",
-             static_cast<long long>(tick));
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(what, sizeof(what), fmt, ap);
+    va_end(ap);
     set_window_work_error(what, pairs, h[3]);
     return SWARM_ERR_RANGE;
 }
@@ -771,39 +779,25 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
         if (n_singular) *n_singular = 0;
         return SWARM_OK;
     }
-    // One grid for the whole call (make_run_grid).  Host wait 1 of 2; non-finite positions are refused here,
+    // One grid for the whole call (loop_sense_begin).  Host wait 1 of 2; non-finite positions are refused here,
     // before anything is written.
-    Grid g;
-    int rc = make_run_grid(ctx, n, pos, sense_radius, steps, dt, max_speed, &g, s);
+    LoopSense ls{};
+    int rc = loop_sense_begin(ctx, n, pos, sense_radius, steps, dt, max_speed, &ls, s);
     if (rc) return rc;
-    double2 *other, *psort;
-    unsigned long long *st;
+    double2 *other;
     SW_ALLOC(other, ctx, S_SENSE_POS, size_t(n) * 16);
-    SW_ALLOC(psort, ctx, S_SENSE_SORTED, size_t(n) * 16);
-    SW_ALLOC(st, ctx, S_SENSE_STATE, 64);
     unsigned long long *h = static_cast<unsigned long long *>(pinned(ctx, 64));
     if (!h) return SWARM_ERR_OOM;
-    SW_HIP(hipMemsetAsync(st, 0, 32, s));
-    const double r2 = sense_radius * sense_radius;
     double2 *buf[2] = {reinterpret_cast<double2 *>(pos), other};
-    const dim3 grid(grid_for(n, kBlock, 8192));
+    // a refused step sets the stop word (ls.st[0]): it and every later step only copy the positions through
     auto queue_step = [&](int32_t k) -> int {
         const double2 *pin = buf[k & 1];
-        int32_t *sorted;
-        uint32_t *off;
-        double *acc;
-        int rc;
-        if ((rc = bin_agents(ctx, n, reinterpret_cast<const double *>(pin), g, &sorted, &off, s))) return rc;
-        // the step's window work against swarm_build_rgg's limits, judged on the device: a refused step
-        // sets the stop word, and it and every later step only copy the positions through
-        if ((rc = launch_window_work(ctx, off, g, s, &acc))) return rc;
-        hipLaunchKernelGGL(k_sense_verdict, dim3(1), dim3(1), 0, s, acc, st, k);
-        SW_LAUNCHED();
-        hipLaunchKernelGGL(k_sorted_positions, grid, dim3(kBlock), 0, s, pin, n, sorted, psort);
-        SW_LAUNCHED();
-        hipLaunchKernelGGL(k_physics_sensed, grid, dim3(kBlock), 0, s, n, ids, state, leader_index, pin,
-                           buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel), reinterpret_cast<double2 *>(target),
-                           has_target, m, obstacles, g, r2, sorted, off, psort, dt, max_speed, st);
+        const int rc = loop_sense_tick(ctx, n, reinterpret_cast<const double *>(pin), k, &ls, s, false);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_physics_sensed, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids, state,
+                           leader_index, pin, buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel),
+                           reinterpret_cast<double2 *>(target), has_target, m, obstacles, ls.g, ls.r2, ls.sorted,
+                           ls.off, ls.psort, dt, max_speed, ls.st);
         SW_LAUNCHED();
         return SWARM_OK;
     };
@@ -814,20 +808,14 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
     for (rc = SWARM_OK; queued < steps; ++queued)
         if ((rc = queue_step(queued))) break;
     if (queued & 1) SW_HIP(hipMemcpyAsync(pos, other, size_t(n) * 16, hipMemcpyDeviceToDevice, s));
-    SW_HIP(hipMemcpyAsync(h, st, 32, hipMemcpyDeviceToHost, s));
+    SW_HIP(hipMemcpyAsync(h, ls.st, 32, hipMemcpyDeviceToHost, s));
     SW_HIP(hipStreamSynchronize(s));  // host wait 2 of 2
     const int32_t done = h[0] ? int32_t(h[0] - 1) : queued;
     if (steps_done) *steps_done = done;
     if (n_singular) *n_singular = int64_t(h[1]);
     if (rc) return rc;
-    if (h[0]) {
-        double pairs;
-        memcpy(&pairs, h + 2, 8);
-        char what[96];
-        snprintf(what, sizeof(what), "agents too dense to sense at step %d (%d steps done)", int(done), int(done));
-        set_window_work_error(what, pairs, h[3]);
-        return SWARM_ERR_RANGE;
-    }
+    if (h[0])
+        return loop_sense_refusal(h, "agents too dense to sense at step %d (%d steps done)", int(done), int(done));
     return SWARM_OK;
 }
 

@@ -36,20 +36,21 @@
 // arithmetic worth the name.
 // Agents killed at a kill tick (every alive LEADER then) stop receiving and sending.
 //
-// swarm_update_loop (contract U1, agent.py:67-81) runs the same ticks, each followed by the physics step
-// of that tick (physics.hip k_physics_loop, on the run's records): the host loop below is shared
-// (run_ticks), the tick kernels are the same and read the heartbeat positions from the lagged one of the
-// loop's two position buffers.  swarm_update_loop_sensed (contract U1-S) is that loop with the separation
-// neighbours of every tick sensed from the tick's snapshot (physics.hip k_physics_loop_sensed): per tick the
-// snapshot is binned and its window work judged before the tick kernel, the tick kernels are untouched, and a
+// swarm_update_loop (contract U1, agent.py:67-81) runs the same ticks, each followed by the physics step of
+// that tick (physics.hip k_physics_loop, on the run's records); the tick kernels are the same and read the
+// heartbeat positions from the lagged one of the loop's two position buffers.  swarm_update_loop_sensed
+// (U1-S) senses every tick's separation neighbours from the tick's snapshot (k_physics_loop_sensed), and a
 // refused tick makes the call restore every caller array on the device (k_restore_refused: all or nothing).
-// swarm_update_loop_radio (contract U1-R) is the sensed loop without a message graph: the tick kernel
-// (k_tick_radio) is k_tick_pull's agent with the row walk replaced by the merge over the agent's 3 x 3 cell
-// window of the same binning, who hears whom judged on the tick's snapshot.
+// swarm_update_loop_radio (U1-R) is the sensed loop without a message graph: k_tick_radio is k_tick_pull's
+// agent with the row walk replaced by the merge over its 3 x 3 cell window of the same binning.
+// The host loop of all five entry points is run_ticks, a sequence of stages that each own their scratch:
+// check_run_args, Counters, pack_records, PushState / RadioState / launch_tick_pull (the receive launch by
+// mode), EntrySnapshot (sensed), TickClocks (A/B aid), tick_physics, read_back (one host wait).
 #include <cmath>
 #include <cstring>
 
 #include "fsm_records.h"
+#include "tick_segments.h"
 #include "window_merge.h"
 
 namespace swarm {
@@ -461,17 +462,12 @@ __global__ __launch_bounds__(kBlock) void k_mail_from_outbox(int64_t n, const ui
 //            order when it has several (multi bit) or the tick is pulled -- then its timers run on
 //            the result.
 // Senders of both roles are listed in the workgroup's own segment, then mailed by it.
-#ifndef SWARM_SWEEP_V  // A/B aid: agents per sweep thread (4 or 8)
-#define SWARM_SWEEP_V 4
-#endif
-constexpr int kSweepV = SWARM_SWEEP_V;
-static_assert(kSweepV == 4 || kSweepV == 8, "sweep: 4 or 8 agents per thread");
-constexpr int kRecvChunk = 4096;  // agents per receive-role pass (64 mail words, 16 agents per thread;
-                                  // 2 048: 0.144 vs 0.138 ms per tick)
+// (kSweepV, kRecvChunk: tick_segments.h, with the arithmetic of the grid and the segment capacities.)
+static_assert(kTickBlock == kBlock, "tick_segments.h sizes the segments for kBlock threads");
 
 // Sender segments of k_tick's workgroups (each mails its own): the g_recv receive-role ones first
 // (rcap entries each: their chunks' agents), then the sweep-role ones (scap each: their agents, or
-// their chunks' on a pulled tick, when every workgroup receives).
+// their chunks' on a pulled tick, when every workgroup receives).  Sized by tick_shape (tick_segments.h).
 struct Segs {
     int32_t *base;
     int64_t rcap, scap;
@@ -1005,322 +1001,436 @@ __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, con
     add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
 }
 
-// The ticks t0+1 .. t0+ticks of swarm_protocol_run_ex, and of swarm_update_loop when `loop` is given (each
-// tick then followed by its physics step; `pos` is not used, the heartbeats read the lagged buffer).
-int run_ticks(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
-              const int32_t *col, const int32_t *hear_row_ptr, const int32_t *hear_col, const int32_t *tick_off,
-              const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt, double timeout, double jitter,
-              uint64_t seed, const int64_t *kill_ticks, int32_t n_kill, double pull_frac, int64_t *counts,
-              int64_t *traffic, const LoopArgs *loop, void *stream) {
-    SW_ARG(ctx != nullptr && fsm != nullptr, "NULL argument");
-    SW_ARG(n >= 0 && n < (int64_t(1) << 31) && ticks >= 0 && t0 >= 0 && n_kill >= 0, "sizes out of range");
-    SW_ARG(n_kill == 0 || kill_ticks != nullptr, "kill_ticks is NULL");
-    SW_ARG(std::isfinite(dt) && timeout >= 0.0 && jitter >= 0.0, "dt / timeout / jitter out of range");
-    SW_ARG(hear_row_ptr != nullptr || hear_col == nullptr, "hear_col without hear_row_ptr");
-    const bool radio = loop && loop->radio_radius > 0.0;
-    SW_ARG(n == 0 || (ids && pos && (row_ptr || radio) && tick_off && fsm->state && fsm->leader && fsm->last_hb &&
-                      fsm->wait_start && fsm->delay && fsm->leader_pos && fsm->has_leader_pos && fsm->alive &&
-                      fsm->outbox),
+// ---------------------------------------------------------------- the host loop, in stages
+// One run's arguments, as the five entry points fill them (`loop`: swarm_update_loop*, each tick then followed
+// by its physics step; `pos` is not used then, the heartbeats read the lagged buffer).
+struct TickRun {
+    swarm_ctx *ctx;
+    int64_t n;
+    const int32_t *ids;
+    const double *pos;
+    const int32_t *row_ptr, *col, *hear_row_ptr, *hear_col, *tick_off;
+    const swarm_fsm *fsm;
+    int64_t t0;
+    int32_t ticks;
+    double dt, timeout, jitter;
+    uint64_t seed;
+    const int64_t *kill_ticks;
+    int32_t n_kill;
+    double pull_frac;
+    int64_t *counts, *traffic;
+    const LoopArgs *loop;
+    void *stream;
+    bool sensed() const { return loop && loop->sense_radius > 0.0; }
+    bool radio() const { return loop && loop->radio_radius > 0.0; }
+    bool push() const { return hear_row_ptr != nullptr; }
+};
+
+// What one tick's receive launch needs, whatever the mode: the heartbeats' positions (the loops: the lagged
+// buffer), tick t-1's sends and tick t's, the tick's kShards x 4 partial counters.
+struct Tick {
+    int64_t t;
+    const double2 *pos;
+    const uint8_t *ob_in;
+    uint8_t *ob_out;
+    unsigned long long *cnt;
+};
+
+int env_int(const char *name) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : 0;
+}
+
+int check_run_args(const TickRun &r) {
+    const swarm_fsm *fsm = r.fsm;
+    SW_ARG(r.ctx != nullptr && fsm != nullptr, "NULL argument");
+    SW_ARG(r.n >= 0 && r.n < (int64_t(1) << 31) && r.ticks >= 0 && r.t0 >= 0 && r.n_kill >= 0, "sizes out of range");
+    SW_ARG(r.n_kill == 0 || r.kill_ticks != nullptr, "kill_ticks is NULL");
+    SW_ARG(std::isfinite(r.dt) && r.timeout >= 0.0 && r.jitter >= 0.0, "dt / timeout / jitter out of range");
+    SW_ARG(r.hear_row_ptr != nullptr || r.hear_col == nullptr, "hear_col without hear_row_ptr");
+    SW_ARG(r.n == 0 || (r.ids && r.pos && (r.row_ptr || r.radio()) && r.tick_off && fsm->state && fsm->leader &&
+                        fsm->last_hb && fsm->wait_start && fsm->delay && fsm->leader_pos && fsm->has_leader_pos &&
+                        fsm->alive && fsm->outbox),
            "NULL agent array");
-    SW_ARG(!std::isnan(pull_frac), "pull_frac is NaN");
-    if (traffic) for (int q = 0; q < kTraffic; ++q) traffic[q] = 0;
-    if (n == 0 || ticks == 0) {
-        if (counts) for (int64_t q = 0; q < int64_t(ticks) * 4; ++q) counts[q] = 0;
+    SW_ARG(!std::isnan(r.pull_frac), "pull_frac is NaN");
+    return SWARM_OK;
+}
+
+// The run's counters in one scratch buffer (S_TMP0), laid out once.
+struct Counters {
+    unsigned long long *part;       // per tick: kShards x 4 partial counters
+    unsigned long long *sums;       // per tick: their 4 sums (k_sum_counts)
+    unsigned long long *tr_shards;  // kShards x kTraffic traffic counters, NULL when no traffic is asked for
+    unsigned long long *tr_sums;    // their kTraffic sums (k_sum_traffic)
+    unsigned long long *sing;       // the loop's singular count: the last 64 bytes of the buffer
+    int lay(const TickRun &r, hipStream_t s) {
+        const size_t ticks = size_t(r.ticks);
+        const size_t part_bytes = ticks * kShards * 4 * 8, tr_bytes = size_t(kShards) * kTraffic * 8;
+        SW_ALLOC(part, r.ctx, S_TMP0, part_bytes + ticks * 4 * 8 + tr_bytes + kTraffic * 8 + 64);
+        sums = part + ticks * kShards * 4;
+        unsigned long long *shards = sums + ticks * 4;
+        tr_shards = r.traffic ? shards : nullptr;
+        tr_sums = shards + size_t(kShards) * kTraffic;
+        sing = tr_sums + kTraffic;
+        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
+        if (tr_shards) SW_HIP(hipMemsetAsync(tr_shards, 0, tr_bytes, s));
+        if (r.loop) SW_HIP(hipMemsetAsync(sing, 0, 8, s));
         return SWARM_OK;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // U1-S: the call's grid (the loop's one host wait before its end; non-finite positions are refused here),
-    // then the caller's arrays as they are now, put back on the device if a tick is refused -- the ticks after
-    // a refused one are already queued and run on the records, so the call is all or nothing
-    const bool sensed = loop && loop->sense_radius > 0.0;
-    LoopSense ls{};
+};
+
+// The sweep role's grid, and every per-agent kernel's of the run: 2 560 workgroups at most, with half as many
+// in the receive role (10M agents, one-launch ticks, two boxes: 0.1208-0.1212 ms per tick against
+// 0.1232-0.1234 for 2 048 + 1 280, 0.122 for 1 536 + 1 280, 2 560 + 1 536 and 3 072 + 1 280; the two-launch
+// form had 2 048 + 1 280 at 0.128, 4 096 + 2 048 at 0.131; SWARM_FSM_SWEEP_WGS overrides, A/B aid)
+unsigned sweep_grid(int64_t n) {
+    static const int sweep_env = env_int("SWARM_FSM_SWEEP_WGS");
+    return grid_for(n, kBlock, sweep_env > 0 ? unsigned(sweep_env) : 2560u);
+}
+
+// The run's records (flag word + timer tick, leader + leader position; unpacked into the caller's arrays at
+// the end of the run), the LRecs on a 16-byte boundary; *vec: the sweep may load words (the outbox 16-byte
+// aligned -- the tick's half is checked per launch; the records are scratch).
+int pack_records(const TickRun &r, unsigned grid, Fsm *f, int *vec, hipStream_t s) {
+    const swarm_fsm *fsm = r.fsm;
+    uint8_t *recs;
+    SW_ALLOC(recs, r.ctx, S_FSM_FLAGS, size_t(r.n) * 24 + 16);
+    *f = Fsm{reinterpret_cast<uint2 *>(recs), reinterpret_cast<LRec *>(recs + lrec_offset(r.n)), fsm->last_hb,
+             fsm->wait_start, fsm->delay, r.t0, r.t0 + r.ticks, r.dt};
+    auto a16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    *vec = a16(fsm->outbox) && a16(recs);
+    SW_ARG((reinterpret_cast<uintptr_t>(fsm->leader_pos) & 7) == 0, "leader_pos is not 8-byte aligned");
+    hipLaunchKernelGGL(k_pack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, fsm->state, fsm->alive, fsm->has_leader_pos,
+                       r.tick_off, fsm->leader, reinterpret_cast<const float2 *>(fsm->leader_pos), *f);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
+// Push mode: the mail words (three buffers rotated by tick, NextMail), the single-sender slots (two, by tick
+// parity), the pull flags (by tick, after the words) and k_tick's sender segments.
+struct PushState {
+    static constexpr int nbuf = 3;
+    int64_t n = 0, n_words = 0;
+    unsigned long long *mw = nullptr;  // buffer b: mail bits at mw + 2b n_words, multi bits after them
+    int32_t *from_base = nullptr;
+    unsigned *pullf = nullptr;         // [nbuf] by tick: the tick pulls
+    TickShape shape{};                 // k_tick's grid (both roles), the XCD-grouped order, the segments' capacities
+    Segs segs{};
+
+    Mail mail_of(int64_t tick) const {  // the mail a tick receives
+        Mail m{};
+        m.bits = mw + size_t(tick % nbuf) * 2 * size_t(n_words);
+        m.multi = m.bits + n_words;
+        m.from = from_base + size_t(tick & 1) * size_t(n);
+        return m;
+    }
+
+    // Scratch, everything cleared, and the mail for tick t0 + 1 from tick t0's sends (a resumed run).
+    int begin(const TickRun &r, unsigned grid, hipStream_t s) {
+        static const int recv_env = env_int("SWARM_FSM_RECV_WGS"), xg_env = env_int("SWARM_TICK_XCD_GROUP");
+        n = r.n;
+        n_words = (n + 63) / 64;
+        shape = tick_shape(n, grid, recv_env, xg_env);
+        SW_ALLOC(mw, r.ctx, S_FSM_MAIL, size_t(n_words) * 48 + 64);
+        SW_ALLOC(from_base, r.ctx, S_FSM_FROM, size_t(n) * 8);
+        segs = Segs{nullptr, shape.rcap, shape.scap, shape.g_recv};
+        SW_ALLOC(segs.base, r.ctx, S_FSM_SEND, size_t(shape.seg_total) * 4);
+        pullf = reinterpret_cast<unsigned *>(mw + 6 * n_words);
+        SW_HIP(hipMemsetAsync(mw, 0, size_t(n_words) * 48 + 64, s));
+        hipLaunchKernelGGL(k_mail_from_outbox, dim3(grid), dim3(kBlock), 0, s, n,
+                           r.fsm->outbox + size_t(r.t0 & 1) * size_t(n), r.hear_row_ptr, r.hear_col,
+                           mail_of(r.t0 + 1));
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+
+    // Tick k.t: receives buf(t), mails into buf(t+1), clears buf(t+2).
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, int vec, unsigned long long *tr, hipStream_t s) const {
+        const int64_t t = k.t;
+        const NextMail im{mail_of(t + 1), mail_of(t + 2).bits, 2 * n_words, pullf + (t + 1) % nbuf,
+                          pullf + (t + 2) % nbuf, r.pull_frac < 0.0 ? -1.0 : r.pull_frac, r.hear_row_ptr,
+                          r.hear_col, r.t0};
+        hipLaunchKernelGGL(k_tick, dim3(shape.tgrid), dim3(kBlock), 0, s, n, t, r.ids, k.pos, r.row_ptr, r.col, f,
+                           mail_of(t), k.ob_in, k.ob_out, pullf + t % nbuf, segs, r.dt, r.timeout, r.jitter, r.seed,
+                           k.cnt, int(vec && (reinterpret_cast<uintptr_t>(k.ob_out) & 3) == 0), tr, im, shape.xg);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+};
+
+// Radio mode (U1-R): no mail bitmap, no sender segments -- the receivers find their senders in their windows
+// of the tick's binning (LoopSense), through a cell-sorted copy of the outbox and a byte per cell.
+struct RadioState {
+    Radio rw{};
+    size_t cells = 0;
+
+    int begin(const TickRun &r, const LoopSense &ls) {
+        rw.g = ls.g;
+        rw.r2 = r.loop->radio_radius * r.loop->radio_radius;
+        rw.st = ls.st;
+        cells = size_t(ls.g.ncx * ls.g.ncy);
+        SW_ALLOC(rw.ob_sorted, r.ctx, S_RADIO_OUTBOX, size_t(r.n));
+        SW_ALLOC(rw.cell_send, r.ctx, S_RADIO_CELLS, cells);
+        return SWARM_OK;
+    }
+
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, hipStream_t s) {
+        const dim3 grid(grid_for(r.n, kBlock, 8192));
+        rw.sorted = ls.sorted;
+        rw.off = ls.off;
+        rw.psort = ls.psort;
+        SW_HIP(hipMemsetAsync(rw.cell_send, 0, cells, s));
+        hipLaunchKernelGGL(k_radio_outbox, grid, dim3(kBlock), 0, s, r.n, k.ob_in, rw);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_tick_radio, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
+                           r.timeout, r.jitter, r.seed, k.cnt);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+};
+
+int launch_tick_pull(const TickRun &r, unsigned grid, const Fsm &f, const Tick &k, hipStream_t s) {
+    hipLaunchKernelGGL(k_tick_pull, dim3(grid), dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, r.row_ptr, r.col, f,
+                       k.ob_in, k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
+// The sensed loops (U1-S, U1-R): the caller's arrays as they are at entry, put back on the device if a tick
+// is refused -- the ticks after a refused one are already queued and run on the records, so the call is all
+// or nothing, and it needs no host wait to decide.
+struct EntrySnapshot {
     struct Kept {
         void *p;
         size_t bytes, at;
     } kept[14];
-    int n_kept = 0;
     uint8_t *snap = nullptr;
-    if (sensed) {
-        // (U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
-        const int rc = loop_sense_begin(ctx, n, loop->pos, loop->sense_radius, ticks, dt, loop->max_speed, &ls, s,
-                                        radio ? loop->radio_radius : 0.0);
-        if (rc) return rc;
-        const size_t un = size_t(n);
+
+    int take(const TickRun &r, hipStream_t s) {
+        const LoopArgs *loop = r.loop;
+        const swarm_fsm *fsm = r.fsm;
+        const size_t un = size_t(r.n);
         const Kept all[14] = {{loop->pos, un * 16, 0},       {loop->pos_prev, un * 16, 0},  {loop->vel, un * 16, 0},
                               {loop->target, un * 16, 0},    {fsm->last_hb, un * 8, 0},     {fsm->wait_start, un * 8, 0},
                               {fsm->delay, un * 8, 0},       {fsm->leader_pos, un * 8, 0},  {fsm->leader, un * 4, 0},
                               {fsm->outbox, un * 2, 0},      {loop->has_target, un, 0},     {fsm->state, un, 0},
                               {fsm->alive, un, 0},           {fsm->has_leader_pos, un, 0}};
         size_t total = 0;
-        for (const Kept &k : all) {
-            kept[n_kept] = k;
-            kept[n_kept++].at = total;
-            total += (k.bytes + 15) & ~size_t(15);
+        for (int q = 0; q < 14; ++q) {
+            kept[q] = all[q];
+            kept[q].at = total;
+            total += (all[q].bytes + 15) & ~size_t(15);
         }
-        SW_ALLOC(snap, ctx, S_LOOP_SNAP, total);
-        for (int q = 0; q < n_kept; ++q)
-            SW_HIP(hipMemcpyAsync(snap + kept[q].at, kept[q].p, kept[q].bytes, hipMemcpyDeviceToDevice, s));
+        SW_ALLOC(snap, r.ctx, S_LOOP_SNAP, total);
+        for (const Kept &k : kept)
+            SW_HIP(hipMemcpyAsync(snap + k.at, k.p, k.bytes, hipMemcpyDeviceToDevice, s));
+        return SWARM_OK;
     }
-    unsigned long long *d_cnt;  // per tick: kShards x 4 partial counters, then the 4 sums
-    const size_t part_bytes = size_t(ticks) * kShards * 4 * 8;
-    const size_t tr_bytes = size_t(kShards) * kTraffic * 8;
-    SW_ALLOC(d_cnt, ctx, S_TMP0, part_bytes + size_t(ticks) * 4 * 8 + tr_bytes + kTraffic * 8 + 64);
-    SW_HIP(hipMemsetAsync(d_cnt, 0, part_bytes, s));
-    unsigned long long *d_sum = d_cnt + size_t(ticks) * kShards * 4;
-    unsigned long long *d_tr = traffic ? d_sum + size_t(ticks) * 4 : nullptr;
-    if (d_tr) SW_HIP(hipMemsetAsync(d_tr, 0, tr_bytes, s));
-    // the loop's singular count: the last 64 bytes of the buffer
-    unsigned long long *d_sing = d_sum + size_t(ticks) * 4 + size_t(kShards) * kTraffic + kTraffic;
-    if (loop) SW_HIP(hipMemsetAsync(d_sing, 0, 8, s));
-    // the run's records (flag word + timer tick, leader + leader position; unpacked into the caller's arrays
-    // at the end of the run), the LRecs on a 16-byte boundary
-    uint8_t *recs;
-    SW_ALLOC(recs, ctx, S_FSM_FLAGS, size_t(n) * 24 + 16);
-    const Fsm f{reinterpret_cast<uint2 *>(recs), reinterpret_cast<LRec *>(recs + lrec_offset(n)), fsm->last_hb,
-                fsm->wait_start, fsm->delay, t0, t0 + ticks, dt};
-    // the sweep role's grid: 2 560 workgroups at most, with half as many in the receive role (10M
-    // agents, one-launch ticks, two boxes: 0.1208-0.1212 ms per tick against 0.1232-0.1234 for
-    // 2 048 + 1 280, 0.122 for 1 536 + 1 280, 2 560 + 1 536 and 3 072 + 1 280; the two-launch form
-    // had 2 048 + 1 280 at 0.128, 4 096 + 2 048 at 0.131; SWARM_FSM_SWEEP_WGS overrides, A/B aid)
-    static const int sweep_env = [] {
-        const char *e = getenv("SWARM_FSM_SWEEP_WGS");
-        return e ? atoi(e) : 0;
-    }();
-    const unsigned grid = grid_for(n, kBlock, sweep_env > 0 ? unsigned(sweep_env) : 2560u);
-    auto a16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    // the sweep's word loads: the outbox 4-byte aligned (the tick's half too; records: scratch)
-    const int vec = a16(fsm->outbox) && a16(recs);
-    SW_ARG((reinterpret_cast<uintptr_t>(fsm->leader_pos) & 7) == 0, "leader_pos is not 8-byte aligned");
-    hipLaunchKernelGGL(k_pack_fsm, dim3(grid), dim3(kBlock), 0, s, n, fsm->state, fsm->alive, fsm->has_leader_pos,
-                       tick_off, fsm->leader, reinterpret_cast<const float2 *>(fsm->leader_pos), f);
-    SW_LAUNCHED();
-    const bool push = hear_row_ptr != nullptr;
-    const int64_t n_words = (n + 63) / 64;
-    Mail mail{};
-    Segs segs{};
-    unsigned *pullf = nullptr;
-    constexpr int nbuf = 3;            // mail word buffers, rotated by tick (NextMail)
-    unsigned long long *mw = nullptr;  // buffer b: mail bits at mw + 2b n_words, multi bits after them
-    int32_t *from_base = nullptr;      // single-sender slots, two buffers by tick parity
-    auto mail_of = [&](int64_t tick) {  // the mail a tick receives
-        Mail m = mail;
-        m.bits = mw + size_t(tick % nbuf) * 2 * size_t(n_words);
-        m.multi = m.bits + n_words;
-        m.from = from_base + size_t(tick & 1) * size_t(n);
-        return m;
-    };
-    // k_tick's receive role: a workgroup per 4 096-agent chunk, at most half the sweep grid (10M
-    // agents: 1 280 of 2 442 chunks' workgroups; two-launch form, sweep grid 2 048: 1 280 -> 0.1279
-    // ms per tick, 1 536 -> 0.1281, 2 048 -> 0.1298, 1 024 -> 0.1303; sweep grid 4 096: 2 048 ->
-    // 0.138, 512 -> 0.160, 256 -> 0.214; SWARM_FSM_RECV_WGS overrides, A/B aid)
-    static const int recv_env = [] {
-        const char *e = getenv("SWARM_FSM_RECV_WGS");
-        return e ? atoi(e) : 0;
-    }();
-    const int64_t nchunks_all = (n + kRecvChunk - 1) / kRecvChunk;
-    const int g_recv = int(std::max<int64_t>(
-        1, std::min<int64_t>(nchunks_all, recv_env > 0 ? recv_env : std::max<int64_t>(1, int64_t(grid) / 2))));
-    const unsigned tgrid = grid + unsigned(g_recv);  // k_tick: both roles
-    // the receive role's XCD-grouped chunk order (SWARM_TICK_XCD_GROUP chunks per group, 0 = plain
-    // grid stride); only when both role grids split evenly over the 8 XCDs
-    static const int xg_env = [] {
-        const char *e = getenv("SWARM_TICK_XCD_GROUP");
-        return e ? atoi(e) : 0;
-    }();
-    const int xg = (xg_env > 0 && g_recv % 8 == 0 && tgrid % 8 == 0) ? xg_env : 0;
-    if (push) {  // mail bitmaps (nbuf buffers) + the pull flags (by tick, nbuf) after them
-        SW_ALLOC(mw, ctx, S_FSM_MAIL, size_t(n_words) * 48 + 64);
-        SW_ALLOC(from_base, ctx, S_FSM_FROM, size_t(n) * 8);
-        // per-workgroup sender segments of k_tick (each workgroup lists at most the agents it sees:
-        // a grid-stride share of kSweepV-agent groups, or of 4 096-agent chunks), then their counts
-        const int64_t ngroups = (n + kSweepV - 1) / kSweepV;
-        const int64_t nchunks = (n + kRecvChunk - 1) / kRecvChunk;
-        segs.g_recv = g_recv;
-        segs.rcap = (nchunks + g_recv - 1) / g_recv * kRecvChunk;
-        segs.scap = std::max((ngroups + int64_t(grid) * kBlock - 1) / (int64_t(grid) * kBlock) * kBlock * kSweepV,
-                             (nchunks + tgrid - 1) / tgrid * kRecvChunk);
-        if (xg) {  // the grouped order may deal a workgroup more chunks than the grid stride: its segment holds them
-            auto most = [&](int64_t nch, int64_t g, int64_t nrole) {  // max chunks of one workgroup
-                const int64_t ngr = (nch + g - 1) / g;
-                int64_t worst = 0;
-                for (int64_t x = 0; x < 8; ++x) {
-                    const int64_t full = ngr > x ? (ngr - 1 - x) / 8 + 1 : 0;  // groups of XCD x
-                    int64_t cx = full * g;
-                    if (full && (x + 8 * (full - 1)) == ngr - 1) cx -= ngr * g - nch;  // its last group is partial
-                    worst = std::max(worst, (cx + nrole / 8 - 1) / (nrole / 8));
-                }
-                return worst;
-            };
-            segs.rcap = std::max(segs.rcap, most(nchunks, xg, g_recv) * kRecvChunk);
-            const int64_t unit = kRecvChunk / 4, nunits = (n + unit - 1) / unit;
-            segs.scap = std::max(segs.scap, most(nunits, 4 * int64_t(xg), tgrid) * unit);
-            segs.rcap = std::max(segs.rcap, segs.scap);  // a pulled tick: the receive-role workgroups too
-        }
-        const size_t seg_total = size_t(g_recv) * segs.rcap + size_t(grid) * segs.scap;
-        SW_ALLOC(segs.base, ctx, S_FSM_SEND, seg_total * 4);
-        pullf = reinterpret_cast<unsigned *>(mw + 6 * n_words);  // [nbuf] by tick: the tick pulls
-        SW_HIP(hipMemsetAsync(mw, 0, size_t(n_words) * 48 + 64, s));
-        hipLaunchKernelGGL(k_mail_from_outbox, dim3(grid), dim3(kBlock), 0, s, n,
-                           fsm->outbox + size_t(t0 & 1) * size_t(n), hear_row_ptr, hear_col, mail_of(t0 + 1));
-        SW_LAUNCHED();
-    }
-#if SWARM_TICK_CLOCKS
-    unsigned long long *clk_buf = nullptr;
-    const char *clk_file = getenv("SWARM_TICK_CLOCKS_FILE");
-    if (push && clk_file) {
-        SW_HIP(hipMalloc(&clk_buf, size_t(ticks) * tgrid * 5 * 8));
-        SW_HIP(hipMemsetAsync(clk_buf, 0, size_t(ticks) * tgrid * 5 * 8, s));
-    }
-    SW_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tick_clk), &clk_buf, sizeof(clk_buf), 0, hipMemcpyHostToDevice, s));
-#endif
-    Radio rw{};
-    if (radio) {  // no mail bitmap, no sender segments: the receivers find their senders in their windows
-        rw.g = ls.g;
-        rw.r2 = loop->radio_radius * loop->radio_radius;
-        rw.st = ls.st;
-        SW_ALLOC(rw.ob_sorted, ctx, S_RADIO_OUTBOX, size_t(n));
-        SW_ALLOC(rw.cell_send, ctx, S_RADIO_CELLS, size_t(ls.g.ncx * ls.g.ncy));
-    }
-    double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
-    for (int64_t t = t0 + 1; t <= t0 + ticks; ++t) {
-        if (loop) pos = lag;  // a heartbeat sent during tick t-1 carries its sender's position of then
-        bool kill = false;
-        for (int32_t k = 0; k < n_kill; ++k) kill |= kill_ticks[k] == t;
-        if (kill) {
-            hipLaunchKernelGGL(k_kill_leaders, dim3(grid), dim3(kBlock), 0, s, n, f.rec);
+
+    // st[0] != 0: every caller array back to its entry bytes (the unpack before it included), on the device.
+    int restore_if_refused(const unsigned long long *st, hipStream_t s) const {
+        for (const Kept &k : kept) {
+            hipLaunchKernelGGL(k_restore_refused, dim3(grid_for(int64_t(k.bytes / 8 + 1), kBlock, 4096)),
+                               dim3(kBlock), 0, s, st, static_cast<uint8_t *>(k.p), snap + k.at, k.bytes);
             SW_LAUNCHED();
         }
-        if (sensed) {  // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell
-            const int rc = loop_sense_tick(ctx, n, cur, int32_t(t - t0 - 1), &ls, s);
-            if (rc) return rc;
-        }
-        const uint8_t *ob_in = fsm->outbox + size_t((t - 1) & 1) * size_t(n);
-        uint8_t *ob_out = fsm->outbox + size_t(t & 1) * size_t(n);
-        unsigned long long *cnt = d_cnt + size_t(t - t0 - 1) * kShards * 4;
-        if (radio) {
-            rw.sorted = ls.sorted;
-            rw.off = ls.off;
-            rw.psort = ls.psort;
-            SW_HIP(hipMemsetAsync(rw.cell_send, 0, size_t(ls.g.ncx * ls.g.ncy), s));
-            hipLaunchKernelGGL(k_radio_outbox, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ob_in, rw);
-            SW_LAUNCHED();
-            hipLaunchKernelGGL(k_tick_radio, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, t, ids,
-                               reinterpret_cast<const double2 *>(pos), f, rw, ob_out, dt, timeout, jitter, seed,
-                               cnt);
-        } else if (push) {
-            NextMail im{};
-            im.next = mail_of(t + 1);
-            im.clear = mail_of(t + 2).bits;
-            im.n_clear = 2 * n_words;
-            im.pull_next = pullf + (t + 1) % nbuf;
-            im.pull_clear = pullf + (t + 2) % nbuf;
-            im.frac = pull_frac < 0.0 ? -1.0 : pull_frac;
-            im.trp = hear_row_ptr;
-            im.tcol = hear_col;
-            im.clk_t0 = t0;
-            hipLaunchKernelGGL(k_tick, dim3(tgrid), dim3(kBlock), 0, s, n, t, ids,
-                               reinterpret_cast<const double2 *>(pos), row_ptr, col, f, mail_of(t), ob_in,
-                               ob_out, pullf + t % nbuf, segs, dt, timeout, jitter, seed, cnt,
-                               int(vec && (reinterpret_cast<uintptr_t>(ob_out) & 3) == 0), d_tr, im, xg);
-        } else {
-            hipLaunchKernelGGL(k_tick_pull, dim3(grid), dim3(kBlock), 0, s, n, t, ids,
-                               reinterpret_cast<const double2 *>(pos), row_ptr, col, f, ob_in, ob_out, dt,
-                               timeout, jitter, seed, cnt);
-        }
-        SW_LAUNCHED();
-        if (loop) {  // the tick's physics: P_{t-1} -> P_t over the lagged buffer, then the roles swap
-            const int rc =
-                sensed ? launch_physics_loop_sensed(n, ids, f.rec, f.lrec, lag, loop->vel, loop->target,
-                                                    loop->has_target, loop->m, loop->obstacles, ls, dt,
-                                                    loop->max_speed, d_sing, s)
-                       : launch_physics_loop(n, ids, f.rec, f.lrec, cur, lag, loop->vel, loop->target,
-                                             loop->has_target, loop->m, loop->obstacles, loop->sense_rp,
-                                             loop->sense_col, dt, loop->max_speed, d_sing, s);
-            if (rc) return rc;
-            std::swap(cur, lag);
-            const int64_t k = t - t0;
-            if (loop->trace_every > 0 && k % loop->trace_every == 0)
-                SW_HIP(hipMemcpyAsync(loop->trace + size_t(k / loop->trace_every - 1) * size_t(n) * 2, cur,
-                                      size_t(n) * 16, hipMemcpyDeviceToDevice, s));
-        }
+        return SWARM_OK;
     }
-    if (loop && cur != loop->pos) {  // an odd number of ticks: pos <- P_end, pos_prev <- P_{end-1}
-        hipLaunchKernelGGL(k_swap_positions, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n,
-                           reinterpret_cast<double2 *>(loop->pos), reinterpret_cast<double2 *>(loop->pos_prev));
-        SW_LAUNCHED();
-    }
+};
+
+// The A/B aid of -DSWARM_TICK_CLOCKS=1 (k_tick's TICK_CLK): the device buffer before the ticks, its records
+// to SWARM_TICK_CLOCKS_FILE after them (header: ticks, workgroups, receive-role workgroups).  Empty otherwise.
+struct TickClocks {
 #if SWARM_TICK_CLOCKS
-    if (clk_buf) {  // experiment aid: header (ticks, workgroups, receive-role workgroups) + the records
-        std::vector<unsigned long long> hc(size_t(ticks) * tgrid * 5);
-        SW_HIP(hipMemcpyAsync(hc.data(), clk_buf, hc.size() * 8, hipMemcpyDeviceToHost, s));
+    unsigned long long *buf = nullptr;
+    const char *file = nullptr;
+    size_t words = 0;
+
+    int begin(const TickRun &r, const PushState &ps, hipStream_t s) {
+        file = getenv("SWARM_TICK_CLOCKS_FILE");
+        words = size_t(r.ticks) * ps.shape.tgrid * 5;
+        if (r.push() && file) {
+            SW_HIP(hipMalloc(&buf, words * 8));
+            SW_HIP(hipMemsetAsync(buf, 0, words * 8, s));
+        }
+        SW_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tick_clk), &buf, sizeof(buf), 0, hipMemcpyHostToDevice, s));
+        return SWARM_OK;
+    }
+
+    int end(const TickRun &r, const PushState &ps, hipStream_t s) {
+        if (!buf) return SWARM_OK;
+        std::vector<unsigned long long> hc(words);
+        SW_HIP(hipMemcpyAsync(hc.data(), buf, words * 8, hipMemcpyDeviceToHost, s));
         SW_HIP(hipStreamSynchronize(s));
-        SW_HIP(hipFree(clk_buf));
-        if (FILE *fp = fopen(clk_file, "wb")) {
-            const long long hdr[3] = {ticks, (long long)tgrid, g_recv};
+        SW_HIP(hipFree(buf));
+        if (FILE *fp = fopen(file, "wb")) {
+            const long long hdr[3] = {r.ticks, (long long)ps.shape.tgrid, ps.shape.g_recv};
             fwrite(hdr, 8, 3, fp);
             fwrite(hc.data(), 8, hc.size(), fp);
             fclose(fp);
         }
-    }
-#endif
-    hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, n, fsm->state, fsm->alive, fsm->has_leader_pos,
-                       fsm->leader, reinterpret_cast<float2 *>(fsm->leader_pos), f);
-    SW_LAUNCHED();
-    if (d_tr) {  // pull-mode runs: every tick walks every row (the receivers are all agents)
-        unsigned long long *hs = static_cast<unsigned long long *>(pinned(ctx, kTraffic * 8));
-        if (!hs) return SWARM_ERR_OOM;
-        hipLaunchKernelGGL(k_sum_traffic, dim3(1), dim3(kWave), 0, s, d_tr, d_tr + size_t(kShards) * kTraffic);
-        SW_LAUNCHED();
-        SW_HIP(hipMemcpyAsync(hs, d_tr + size_t(kShards) * kTraffic, kTraffic * 8, hipMemcpyDeviceToHost, s));
-        SW_HIP(hipStreamSynchronize(s));
-        for (int q = 0; q < kTraffic; ++q) traffic[q] = int64_t(hs[q]);
-    }
-    if (sensed) {
-        // a refused tick: every caller array back to its entry bytes (the unpack above included), all on the
-        // device; then the verdict, the singular count and the counts come back through pinned memory in the
-        // call's one final host wait, and the counts reach the caller only when no tick was refused
-        for (int q = 0; q < n_kept; ++q) {
-            hipLaunchKernelGGL(k_restore_refused, dim3(grid_for(int64_t(kept[q].bytes / 8 + 1), kBlock, 4096)),
-                               dim3(kBlock), 0, s, ls.st, static_cast<uint8_t *>(kept[q].p), snap + kept[q].at,
-                               kept[q].bytes);
-            SW_LAUNCHED();
-        }
-        const size_t cnt_bytes = counts ? size_t(ticks) * 4 * 8 : 0;
-        unsigned long long *h = static_cast<unsigned long long *>(pinned(ctx, 64 + cnt_bytes));
-        if (!h) return SWARM_ERR_OOM;
-        SW_HIP(hipMemcpyAsync(h, ls.st, 32, hipMemcpyDeviceToHost, s));
-        SW_HIP(hipMemcpyAsync(h + 4, d_sing, 8, hipMemcpyDeviceToHost, s));
-        if (counts) {
-            hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
-                               int64_t(ticks), d_cnt, d_sum);
-            SW_LAUNCHED();
-            SW_HIP(hipMemcpyAsync(h + 8, d_sum, cnt_bytes, hipMemcpyDeviceToHost, s));
-        }
-        SW_HIP(hipStreamSynchronize(s));
-        if (h[0]) {
-            const int64_t tick = t0 + int64_t(h[0]);
-            if (loop->refused_tick) *loop->refused_tick = tick;
-            return loop_sense_refusal(h, tick);
-        }
-        if (loop->n_singular) *loop->n_singular = int64_t(h[4]);
-        if (counts) memcpy(counts, h + 8, cnt_bytes);
         return SWARM_OK;
     }
-    unsigned long long *h_sing = nullptr;
-    if (loop && loop->n_singular) {  // read back with the counts: the run's one host wait
-        h_sing = static_cast<unsigned long long *>(pinned(ctx, 64));
-        if (!h_sing) return SWARM_ERR_OOM;
-        SW_HIP(hipMemcpyAsync(h_sing, d_sing, 8, hipMemcpyDeviceToHost, s));
-    }
-    if (counts) {
-        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
-                           int64_t(ticks), d_cnt, d_sum);
-        SW_LAUNCHED();
-        SW_HIP(hipMemcpyAsync(counts, d_sum, size_t(ticks) * 4 * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (counts || h_sing) SW_HIP(hipStreamSynchronize(s));
-    if (h_sing) *loop->n_singular = int64_t(*h_sing);
+#else
+    int begin(const TickRun &, const PushState &, hipStream_t) { return SWARM_OK; }
+    int end(const TickRun &, const PushState &, hipStream_t) { return SWARM_OK; }
+#endif
+};
+
+// The tick's physics: P_{t-1} (cur) -> P_t over the lagged buffer, then the roles swap; the trace frame.
+int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t, double **cur, double **lag,
+                 unsigned long long *sing, hipStream_t s) {
+    const LoopArgs *loop = r.loop;
+    const int rc = r.sensed() ? launch_physics_loop_sensed(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
+                                                           loop->has_target, loop->m, loop->obstacles, ls, r.dt,
+                                                           loop->max_speed, sing, s)
+                              : launch_physics_loop(r.n, r.ids, f.rec, f.lrec, *cur, *lag, loop->vel, loop->target,
+                                                    loop->has_target, loop->m, loop->obstacles, loop->sense_rp,
+                                                    loop->sense_col, r.dt, loop->max_speed, sing, s);
+    if (rc) return rc;
+    std::swap(*cur, *lag);
+    const int64_t k = t - r.t0;
+    if (loop->trace_every > 0 && k % loop->trace_every == 0)
+        SW_HIP(hipMemcpyAsync(loop->trace + size_t(k / loop->trace_every - 1) * size_t(r.n) * 2, *cur,
+                              size_t(r.n) * 16, hipMemcpyDeviceToDevice, s));
     return SWARM_OK;
+}
+
+// The run's results: the traffic sums, (sensed) the verdict words, the loop's singular count and the counts
+// come back through pinned memory -- [0..3] verdict, [4] singular, [8..15] traffic, [16..] counts -- in the
+// run's one final host wait (none when nothing is asked for).  A refused tick (`snap` restores the caller's
+// arrays) withholds the counts and the singular count and sets refused_tick.
+int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap, hipStream_t s) {
+    const bool want_sing = r.loop && r.loop->n_singular;
+    if (r.traffic) {  // (pull-mode runs: every tick walks every row -- the receivers are all agents)
+        hipLaunchKernelGGL(k_sum_traffic, dim3(1), dim3(kWave), 0, s, c.tr_shards, c.tr_sums);
+        SW_LAUNCHED();
+    }
+    if (ls)
+        if (const int rc = snap.restore_if_refused(ls->st, s)) return rc;
+    if (!(r.traffic || ls || want_sing || r.counts)) return SWARM_OK;
+    const size_t cnt_bytes = r.counts ? size_t(r.ticks) * 4 * 8 : 0;
+    unsigned long long *h = static_cast<unsigned long long *>(pinned(r.ctx, 128 + cnt_bytes));
+    if (!h) return SWARM_ERR_OOM;
+    if (r.traffic) SW_HIP(hipMemcpyAsync(h + 8, c.tr_sums, kTraffic * 8, hipMemcpyDeviceToHost, s));
+    if (ls) SW_HIP(hipMemcpyAsync(h, ls->st, 32, hipMemcpyDeviceToHost, s));
+    if (want_sing) SW_HIP(hipMemcpyAsync(h + 4, c.sing, 8, hipMemcpyDeviceToHost, s));
+    if (r.counts) {
+        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
+                           int64_t(r.ticks), c.part, c.sums);
+        SW_LAUNCHED();
+        SW_HIP(hipMemcpyAsync(h + 16, c.sums, cnt_bytes, hipMemcpyDeviceToHost, s));
+    }
+    SW_HIP(hipStreamSynchronize(s));
+    if (r.traffic) for (int q = 0; q < kTraffic; ++q) r.traffic[q] = int64_t(h[8 + q]);
+    if (ls && h[0]) {
+        const int64_t tick = r.t0 + int64_t(h[0]);
+        if (r.loop->refused_tick) *r.loop->refused_tick = tick;
+        return loop_sense_refusal(h, "agents too dense to sense at tick %lld (nothing of the call is kept)",
+                                  static_cast<long long>(tick));
+    }
+    if (want_sing) *r.loop->n_singular = int64_t(h[4]);
+    if (r.counts) memcpy(r.counts, h + 16, cnt_bytes);
+    return SWARM_OK;
+}
+
+// The ticks t0+1 .. t0+ticks of every entry point below.
+int run_ticks(const TickRun &r) {
+    int rc;
+    if ((rc = check_run_args(r))) return rc;
+    if (r.traffic) for (int q = 0; q < kTraffic; ++q) r.traffic[q] = 0;
+    if (r.n == 0 || r.ticks == 0) {
+        if (r.counts) for (int64_t q = 0; q < int64_t(r.ticks) * 4; ++q) r.counts[q] = 0;
+        return SWARM_OK;
+    }
+    hipStream_t s = static_cast<hipStream_t>(r.stream);
+    const LoopArgs *loop = r.loop;
+    const bool sensed = r.sensed(), radio = r.radio(), push = r.push();
+    // U1-S / U1-R: the call's grid (the loop's one host wait before its end; non-finite positions are refused
+    // here; U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
+    LoopSense ls{};
+    EntrySnapshot snap;
+    if (sensed) {
+        if ((rc = loop_sense_begin(r.ctx, r.n, loop->pos, loop->sense_radius, r.ticks, r.dt, loop->max_speed, &ls, s,
+                                   radio ? loop->radio_radius : 0.0)))
+            return rc;
+        if ((rc = snap.take(r, s))) return rc;
+    }
+    Counters cnt;
+    if ((rc = cnt.lay(r, s))) return rc;
+    const unsigned grid = sweep_grid(r.n);
+    Fsm f;
+    int vec;
+    if ((rc = pack_records(r, grid, &f, &vec, s))) return rc;
+    PushState ps;
+    RadioState rs;
+    TickClocks clk;
+    if (push && (rc = ps.begin(r, grid, s))) return rc;
+    if ((rc = clk.begin(r, ps, s))) return rc;
+    if (radio && (rc = rs.begin(r, ls))) return rc;
+    double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
+    for (int64_t t = r.t0 + 1; t <= r.t0 + r.ticks; ++t) {
+        // (a heartbeat sent during tick t-1 carries its sender's position of then: the loops' lagged buffer)
+        const Tick k{t, reinterpret_cast<const double2 *>(loop ? lag : r.pos),
+                     r.fsm->outbox + size_t((t - 1) & 1) * size_t(r.n), r.fsm->outbox + size_t(t & 1) * size_t(r.n),
+                     cnt.part + size_t(t - r.t0 - 1) * kShards * 4};
+        if (std::find(r.kill_ticks, r.kill_ticks + r.n_kill, t) != r.kill_ticks + r.n_kill) {
+            hipLaunchKernelGGL(k_kill_leaders, dim3(grid), dim3(kBlock), 0, s, r.n, f.rec);
+            SW_LAUNCHED();
+        }
+        // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell (the call's grid reaches
+        // far beyond the agents: offsets by search)
+        if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
+        rc = radio  ? rs.launch(r, f, k, ls, s)
+             : push ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
+                    : launch_tick_pull(r, grid, f, k, s);
+        if (rc) return rc;
+        if (loop && (rc = tick_physics(r, f, ls, t, &cur, &lag, cnt.sing, s))) return rc;
+    }
+    if (loop && cur != loop->pos) {  // an odd number of ticks: pos <- P_end, pos_prev <- P_{end-1}
+        hipLaunchKernelGGL(k_swap_positions, dim3(grid_for(r.n, kBlock, 8192)), dim3(kBlock), 0, s, r.n,
+                           reinterpret_cast<double2 *>(loop->pos), reinterpret_cast<double2 *>(loop->pos_prev));
+        SW_LAUNCHED();
+    }
+    if ((rc = clk.end(r, ps, s))) return rc;
+    hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, r.fsm->state, r.fsm->alive,
+                       r.fsm->has_leader_pos, r.fsm->leader, reinterpret_cast<float2 *>(r.fsm->leader_pos), f);
+    SW_LAUNCHED();
+    return read_back(r, cnt, sensed ? &ls : nullptr, snap, s);
+}
+
+// The three loop entry points' own arguments (run_ticks checks the rest): U1 takes a sensor CSR and n < 2^31,
+// U1-S and U1-R sense (kMergeEnd = 2^31 - 1 is no agent: n < 2^31 - 1), U1-R hears by radius as well.
+enum LoopKind { kLoopCsr, kLoopSensed, kLoopRadio };
+
+int check_loop_args(LoopKind kind, swarm_ctx *ctx, int64_t n, int32_t ticks, double dt, const LoopArgs &a) {
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(n >= 0 && n < (int64_t(1) << 31) - (kind == kLoopCsr ? 0 : 1) && a.m >= 0 && ticks >= 0,
+           "sizes out of range");
+    if (kind == kLoopRadio)
+        SW_ARG(a.radio_radius > 0 && std::isfinite(a.radio_radius), "radio_radius must be positive and finite");
+    if (kind != kLoopCsr)
+        SW_ARG(a.sense_radius > 0 && std::isfinite(a.sense_radius), "sense_radius must be positive and finite");
+    SW_ARG(std::isfinite(dt) && std::isfinite(a.max_speed), "dt / max_speed must be finite");
+    SW_ARG(n == 0 || (a.pos && a.pos_prev && a.vel && a.target && a.has_target && (kind != kLoopCsr || a.sense_rp)),
+           "NULL agent array");
+    SW_ARG(a.m == 0 || a.obstacles != nullptr, "obstacles is NULL");
+    SW_ARG(a.trace_every >= 0, "trace_every must not be negative");
+    SW_ARG(n == 0 || a.trace_every == 0 || ticks / a.trace_every == 0 || a.trace != nullptr, "trace is NULL");
+    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
+        const uintptr_t p = reinterpret_cast<uintptr_t>(a.pos), q = reinterpret_cast<uintptr_t>(a.pos_prev);
+        SW_ARG((p > q ? p - q : q - p) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
+        SW_ARG((p & 15) == 0 && (q & 15) == 0, "pos / pos_prev are not 16-byte aligned");
+    }
+    return SWARM_OK;
+}
+
+// A loop entry point: its checks, its outputs' resting values, the run.
+int run_loop(LoopKind kind, const TickRun &r) {
+    if (const int rc = check_loop_args(kind, r.ctx, r.n, r.ticks, r.dt, *r.loop)) return rc;
+    if (r.loop->n_singular) *r.loop->n_singular = 0;
+    if (r.loop->refused_tick) *r.loop->refused_tick = -1;
+    return run_ticks(r);
 }
 
 }  // namespace
@@ -1333,8 +1443,8 @@ int swarm_protocol_run(swarm_ctx *ctx, int64_t n, const int32_t *ids, const doub
                        const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
                        double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
                        int32_t n_kill, int64_t *counts, void *stream) {
-    return swarm::run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
-                            timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, nullptr, stream);
+    return swarm::run_ticks({ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
+                             timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, nullptr, stream});
 }
 
 int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const double *pos, const int32_t *row_ptr,
@@ -1342,8 +1452,8 @@ int swarm_protocol_run_ex(swarm_ctx *ctx, int64_t n, const int32_t *ids, const d
                           const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
                           double dt, double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
                           int32_t n_kill, double pull_frac, int64_t *counts, int64_t *traffic, void *stream) {
-    return swarm::run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
-                            timeout, jitter, seed, kill_ticks, n_kill, pull_frac, counts, traffic, nullptr, stream);
+    return swarm::run_ticks({ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
+                             timeout, jitter, seed, kill_ticks, n_kill, pull_frac, counts, traffic, nullptr, stream});
 }
 
 int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
@@ -1355,23 +1465,10 @@ int swarm_update_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos
                       const int32_t *sense_col, double max_speed, double *trace, int32_t trace_every,
                       int64_t *counts, int64_t *n_singular, void *stream) {
     using namespace swarm;
-    SW_ARG(ctx != nullptr, "ctx is NULL");
-    SW_ARG(n >= 0 && n < (int64_t(1) << 31) && m >= 0 && ticks >= 0, "sizes out of range");
-    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
-    SW_ARG(n == 0 || (pos && pos_prev && vel && target && has_target && sense_row_ptr), "NULL agent array");
-    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
-    SW_ARG(trace_every >= 0, "trace_every must not be negative");
-    SW_ARG(n == 0 || trace_every == 0 || ticks / trace_every == 0 || trace != nullptr, "trace is NULL");
-    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
-        const uintptr_t a = reinterpret_cast<uintptr_t>(pos), b = reinterpret_cast<uintptr_t>(pos_prev);
-        SW_ARG((a > b ? a - b : b - a) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
-        SW_ARG((a & 15) == 0 && (b & 15) == 0, "pos / pos_prev are not 16-byte aligned");
-    }
-    if (n_singular) *n_singular = 0;
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, sense_row_ptr, sense_col, max_speed,
                         trace, trace_every, n_singular, 0.0, nullptr};
-    return run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt, timeout,
-                     jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream);
+    return run_loop(kLoopCsr, {ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt,
+                               timeout, jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream});
 }
 
 int swarm_update_loop_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
@@ -1383,25 +1480,11 @@ int swarm_update_loop_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, doub
                              double sense_radius, double max_speed, double *trace, int32_t trace_every,
                              int64_t *counts, int64_t *n_singular, int64_t *refused_tick, void *stream) {
     using namespace swarm;
-    SW_ARG(ctx != nullptr, "ctx is NULL");
-    SW_ARG(n >= 0 && n < (int64_t(1) << 31) - 1 && m >= 0 && ticks >= 0, "sizes out of range");
-    SW_ARG(sense_radius > 0 && std::isfinite(sense_radius), "sense_radius must be positive and finite");
-    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
-    SW_ARG(n == 0 || (pos && pos_prev && vel && target && has_target), "NULL agent array");
-    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
-    SW_ARG(trace_every >= 0, "trace_every must not be negative");
-    SW_ARG(n == 0 || trace_every == 0 || ticks / trace_every == 0 || trace != nullptr, "trace is NULL");
-    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
-        const uintptr_t a = reinterpret_cast<uintptr_t>(pos), b = reinterpret_cast<uintptr_t>(pos_prev);
-        SW_ARG((a > b ? a - b : b - a) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
-        SW_ARG((a & 15) == 0 && (b & 15) == 0, "pos / pos_prev are not 16-byte aligned");
-    }
-    if (n_singular) *n_singular = 0;
-    if (refused_tick) *refused_tick = -1;
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
                         trace, trace_every, n_singular, sense_radius, refused_tick};
-    return run_ticks(ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks, dt, timeout,
-                     jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop, stream);
+    return run_loop(kLoopSensed, {ctx, n, ids, pos, row_ptr, col, hear_row_ptr, hear_col, tick_off, fsm, t0, ticks,
+                                  dt, timeout, jitter, seed, kill_ticks, n_kill, pull_frac, counts, nullptr, &loop,
+                                  stream});
 }
 
 int swarm_update_loop_radio(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
@@ -1412,26 +1495,10 @@ int swarm_update_loop_radio(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
                             int64_t *refused_tick, void *stream) {
     using namespace swarm;
-    SW_ARG(ctx != nullptr, "ctx is NULL");
-    SW_ARG(n >= 0 && n < (int64_t(1) << 31) - 1 && m >= 0 && ticks >= 0, "sizes out of range");
-    SW_ARG(radio_radius > 0 && std::isfinite(radio_radius), "radio_radius must be positive and finite");
-    SW_ARG(sense_radius > 0 && std::isfinite(sense_radius), "sense_radius must be positive and finite");
-    SW_ARG(std::isfinite(dt) && std::isfinite(max_speed), "dt / max_speed must be finite");
-    SW_ARG(n == 0 || (pos && pos_prev && vel && target && has_target), "NULL agent array");
-    SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
-    SW_ARG(trace_every >= 0, "trace_every must not be negative");
-    SW_ARG(n == 0 || trace_every == 0 || ticks / trace_every == 0 || trace != nullptr, "trace is NULL");
-    if (n > 0) {  // the two position buffers are both read and written by every tick: no shared element
-        const uintptr_t a = reinterpret_cast<uintptr_t>(pos), b = reinterpret_cast<uintptr_t>(pos_prev);
-        SW_ARG((a > b ? a - b : b - a) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
-        SW_ARG((a & 15) == 0 && (b & 15) == 0, "pos / pos_prev are not 16-byte aligned");
-    }
-    if (n_singular) *n_singular = 0;
-    if (refused_tick) *refused_tick = -1;
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
                         trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
-    return run_ticks(ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt, timeout,
-                     jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream);
+    return run_loop(kLoopRadio, {ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+                                 timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream});
 }
 
 }  // extern "C"
