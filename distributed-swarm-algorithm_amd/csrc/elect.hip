@@ -109,8 +109,10 @@ __device__ __forceinline__ void bookkeeping(unsigned long long *ring, unsigned l
 // workgroups one chunk fewer than the first ones, so the dependent load is off the round's
 // critical path.  (Done synchronously: a shard sum held in registers through the gather was
 // spilled to scratch by every thread of every workgroup -- 4 MB written per round.)
-__device__ __forceinline__ void bookkeeping_last(unsigned long long *ring, unsigned long long *tot, int t) {
-    if (blockIdx.x != gridDim.x - 1) return;
+// ng: the grid size, a kernel argument (gridDim.x is a hidden argument, one more scalar load).
+__device__ __forceinline__ void bookkeeping_last(unsigned long long *ring, unsigned long long *tot, int t,
+                                                 uint32_t ng) {
+    if (blockIdx.x != ng - 1) return;
     if (tot && t > 1 && threadIdx.x < kWave) {
         unsigned long long v = *slot(ring, t - 1, C_CHG, threadIdx.x);
 #pragma unroll
@@ -676,13 +678,43 @@ __device__ __forceinline__ void flush_counts(unsigned long long *ring, int t, lo
     }
 }
 
+// What a sparse round needs only after its stamp words are requested: one by-value struct BEHIND the
+// kernel's leading arguments (a by-value struct ends the run of arguments the hardware can preload
+// into SGPRs).  Resolved by the host per launch: no round-parity indexing in the kernel.
+template <typename Off, typename CT>
+struct SparseRest {
+    int32_t *Q;                       // leaders written: L[t & 1]
+    uint8_t *aw;                      // marks written: act[(t + 1) & 1], layout wsm
+    unsigned long long *ring, *tot;
+    int64_t n_rows, c_lo, n_count;    // Frontier's
+    StampMap sm, wsm;                 // Frontier's
+    CT cols;
+    const Off *hrp;                   // DIR: who hears each agent
+    const int32_t *hcol;
+};
+
+// k_sparse_block's flags argument
+constexpr unsigned SF_CLEAR = 1u;        // zero every stamp word after loading it (the next round's 256-round clear)
+constexpr unsigned SF_GUARD_EARLY = 2u;  // SWARM_GUARD_LATE=0: the guard word read and waited for before the stamps
+
+// A wave-uniform 8-byte word no thread of this kernel writes, read with a scalar load (the scalar cache
+// is invalidated at kernel start, so a word the previous kernel wrote is read from L2 or beyond).
+__device__ __forceinline__ unsigned long long scalar_ld8(const unsigned long long *p) {
+    return *(const __attribute__((address_space(4))) unsigned long long *)(p);
+}
+
 // One workgroup per chunk of kBlock * S agents: S stamps per thread, the chunk's marked agents
 // compacted in LDS and gathered by the whole workgroup.
+// The start of a round is one memory round trip: the leading arguments (13 dwords, preloaded into SGPRs
+// where the Makefile's KERNARG_PRELOAD and the firmware allow) are all the stamp loads need -- ar, the
+// stamp words round t reads; nchunks and ng (the grid size).  guard_word: &tot[(t - 2) % kRing] or
+// NULL (guard off); stamp4: round t's stamp byte in all four bytes.
 template <typename Off, int S = kScan, bool DIR = false, typename CT = Col32, int G = kG, int K = kKs,
           bool PRUNE = false>
 __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_block(
-    const Off *__restrict__ rp, CT cols, Frontier f, int t, int guard,
-    const Off *__restrict__ hrp = nullptr, const int32_t *__restrict__ hcol = nullptr) {
+    uint8_t *__restrict__ ar, const unsigned long long *guard_word, const int32_t *__restrict__ P,
+    const Off *__restrict__ rp, uint32_t nchunks, uint32_t ng, int t, unsigned stamp4, unsigned flags,
+    SparseRest<Off, CT> a) {
     using W = typename StampWord<S>::T;
     constexpr int kChunk = kBlock * S;
     __shared__ int s_list[kListCap];
@@ -694,22 +726,6 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
     long long ph_sum = 0, ph_max = 0;
     unsigned long long ph_stamps = 0, ph_listed = 0, ph_gathered = 0;
 #endif
-    bookkeeping_last(f.ring, f.tot, t);
-    // single-GPU runs: round t-2 changed nothing => round t-1 had no marked agent => neither t.
-    // Loaded here, tested only once the first stamp words are in flight (no dependent load in
-    // front of the round's own chain).
-    const unsigned long long prev2 = (guard && t > 2) ? f.tot[(t - 2) % kRing] : 1ull;
-    const int32_t *__restrict__ P = f.L[(t - 1) & 1];
-    int32_t *__restrict__ Q = f.L[t & 1];
-    uint8_t *ar = f.act[t & 1], *aw = f.act[(t + 1) & 1];
-    const unsigned stamp4 = unsigned(stamp_of(t)) * 0x01010101u;
-    const uint8_t sw = stamp_of(t + 1);
-    const int64_t n = f.n_rows;
-    long long my_chg = 0;
-    int my_act = 0, my_edges = 0;
-    const int64_t nchunks = f.sm.M;  // chunk k: stamp slots [k*kChunk, (k+1)*kChunk)
-    const int64_t NG = gridDim.x;
-    const int j0 = threadIdx.x * S;  // this thread's S slots: consecutive agents of one block
     // The stamp words of all this workgroup's chunks (grid-stride, up to kPre at a time) are loaded
     // at once, with clamped addresses so that no load waits on a branch; their marked lanes are
     // kept as S bits per chunk.  The marked agents of all those chunks then go into ONE list in
@@ -718,28 +734,72 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
     // independent of the others within a round.)
     constexpr int kPre = 32 / S < 4 ? 32 / S : 4;
     constexpr int kLogS = S == 8 ? 3 : 1;
-    int listed = 0;  // workgroup-uniform
-    for (int64_t cg = blockIdx.x; cg < nchunks; cg += NG * kPre) {
-        W wv[kPre];
+    const uint32_t NG = ng;  // chunk k: stamp slots [k*kChunk, (k+1)*kChunk); 32-bit chunk numbers
+                             // (nchunks <= 2^22 for n < 2^31, ng * kPre <= 2^17)
+    W wv[kPre];
+    auto load_group = [&](uint32_t cg) {
 #pragma unroll
         for (int p = 0; p < kPre; ++p) {
             // past the end: this thread's own first word again (a shared fallback address would
             // put every workgroup's redundant loads on one L2 channel)
-            const int64_t chunk = cg + p * NG < nchunks ? cg + p * NG : cg;
+            const uint32_t chunk = cg + p * NG < nchunks ? cg + p * NG : cg;
             // chunk base uniform (SGPRs), 32-bit lane offset: no 64-bit per-lane address kept live
-            wv[p] = *reinterpret_cast<const W *>(ar + chunk * kChunk + uint32_t(threadIdx.x * sizeof(W)));
+            wv[p] = *reinterpret_cast<const W *>(ar + size_t(chunk) * kChunk + uint32_t(threadIdx.x * sizeof(W)));
         }
-        if (prev2 == 0) break;  // converged: nothing is marked
+        // SF_CLEAR (the rounds before a 256-round clear point, launch_frontier_round): this buffer is the
+        // one the next round marks into, and this round is its last reader -- every word of a real chunk
+        // is zeroed behind its load (coalesced, fire and forget) instead of a memset between the rounds
+        if (flags & SF_CLEAR) {
+#pragma unroll
+            for (int p = 0; p < kPre; ++p)
+                if (cg + p * NG < nchunks)
+                    *reinterpret_cast<W *>(ar + size_t(cg + p * NG) * kChunk + uint32_t(threadIdx.x * sizeof(W))) = W{};
+        }
+    };
+    // single-GPU runs: round t-2 changed nothing => round t-1 had no marked agent => neither t.
+    // The guard word was written by the previous launch (an L2 miss for most XCDs).  The round's first
+    // instructions are its first stamp loads, which need the leading arguments only (the grid is never
+    // larger than nchunks); the guard word is a scalar load behind them, tested where the stamp words are
+    // first needed, and the last workgroup's bookkeeping comes at the kernel's end: no wait in front of the
+    // round's own chain.  SF_GUARD_EARLY reads and waits for the word first (the former order, for A/B).
+    unsigned long long prev2 = 1ull;
+    if (guard_word && (flags & SF_GUARD_EARLY)) {  // (an atomic load: a vector load, waited for at once)
+        prev2 = __hip_atomic_load(guard_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    load_group(blockIdx.x);
+    if (guard_word && !(flags & SF_GUARD_EARLY)) prev2 = scalar_ld8(guard_word);
+    __builtin_amdgcn_sched_barrier(0);  // nothing that waits for a struct field moves in front of the loads
+    int32_t *__restrict__ Q = a.Q;
+    uint8_t *aw = a.aw;
+    const CT cols = a.cols;
+    const Off *__restrict__ hrp = a.hrp;
+    const int32_t *__restrict__ hcol = a.hcol;
+    const uint8_t sw = stamp_of(t + 1);
+    const int64_t n = a.n_rows;
+    long long my_chg = 0;
+    int my_act = 0, my_edges = 0;
+    const int j0 = threadIdx.x * S;  // this thread's S slots: consecutive agents of one block
+    int listed = 0;  // workgroup-uniform
+    // marked lanes of the group loaded last (only the masks live on from one group to the next: stamp
+    // words kept across the gather are spilled)
+    auto group_masks = [&](uint32_t cg) {
         unsigned masks = 0;
 #pragma unroll
         for (int p = 0; p < kPre; ++p) {
-            const int64_t chunk = cg + p * NG;
+            const uint32_t chunk = cg + p * NG;
             if (chunk < nchunks)
-                masks |= take_stamps<S>(stamp_agent(f.sm, chunk, j0), n, wv[p], stamp4) << (p * S);
+                masks |= take_stamps<S>(stamp_agent(a.sm, chunk, j0), n, wv[p], stamp4) << (p * S);
         }
+        return masks;
+    };
+    uint32_t cg = blockIdx.x;
+    bool more = prev2 != 0;  // converged: nothing is marked
+    unsigned masks = more ? group_masks(cg) : 0u;
 #ifdef SWARM_PHASES
-        if (!ph_stamps) ph_stamps = wall_clock64() + (masks & 0);
+    ph_stamps = wall_clock64() + (masks & 0);
 #endif
+    while (more) {
         // append the group's marked agents, gathering whenever the list fills up
         for (;;) {
             const int cnt = __popc(masks);  // <= kPre * S <= 32
@@ -763,27 +823,35 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
             while (masks && pos < kListCap) {
                 const int bit = __ffs(masks) - 1;
                 masks &= masks - 1;
-                s_list[pos++] = int(stamp_agent(f.sm, cg + (bit >> kLogS) * NG, j0)) + (bit & (S - 1));
+                s_list[pos++] = int(stamp_agent(a.sm, cg + (bit >> kLogS) * NG, j0)) + (bit & (S - 1));
             }
             listed = listed + total < kListCap ? listed + total : kListCap;
             __syncthreads();  // list entries visible
             if (listed < kListCap) break;  // everything fitted
-            gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, f.wsm, sw, s_list, listed, wid * (64 / G),
-                                          kBlock / G, f.c_lo, f.n_count, my_chg, my_act, my_edges);
+            gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
+                                          kBlock / G, a.c_lo, a.n_count, my_chg, my_act, my_edges);
             listed = 0;
             __syncthreads();  // the list is reused
+        }
+        cg += NG * kPre;
+        more = cg < nchunks;
+        if (more) {
+            load_group(cg);
+            masks = group_masks(cg);
         }
     }
 #ifdef SWARM_PHASES
     ph_listed = wall_clock64();
 #endif
     if (listed > 0)
-        gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, f.wsm, sw, s_list, listed, wid * (64 / G),
-                                      kBlock / G, f.c_lo, f.n_count, my_chg, my_act, my_edges);
+        gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
+                                      kBlock / G, a.c_lo, a.n_count, my_chg, my_act, my_edges);
 #ifdef SWARM_PHASES
     ph_gathered = wall_clock64() + (my_chg & 0);
 #endif
-    flush_counts(f.ring, t, my_chg, my_act, my_edges, s_red);
+    // (behind the workgroup's own round: in front of it the stamp words it holds in flight were spilled)
+    bookkeeping_last(a.ring, a.tot, t, ng);
+    flush_counts(a.ring, t, my_chg, my_act, my_edges, s_red);
 #ifdef SWARM_PHASES
     if (threadIdx.x == 0 && blockIdx.x < 8192) {
         g_phase[blockIdx.x * 8 + 0] = ph_t0;
@@ -1160,6 +1228,44 @@ __global__ void k_batch_totals(unsigned long long *ring, int t0, unsigned long l
     }
 }
 
+// k_batch_totals for rounds t0 .. t0 + nr - 1 and k_signal in one launch: ONE workgroup, a wave per round
+// (two rounds' eight shard loads in flight per lane), every wave's totals fenced at system scope, then the
+// epoch word *w = v behind them.
+constexpr int kReadbackThreads = 1024;
+__global__ __launch_bounds__(kReadbackThreads) void k_batch_totals_signal(unsigned long long *ring, int t0, int nr,
+                                                                          unsigned long long *totals,
+                                                                          unsigned long long *w, unsigned long long v) {
+    constexpr int kW = kReadbackThreads / kWave;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    for (int i = wid; i < nr; i += 2 * kW) {
+        const int i2 = i + kW < nr ? i + kW : i;  // the wave's second round (past the end: the first again)
+        unsigned long long x[2 * kCounters];
+#pragma unroll
+        for (int c = 0; c < kCounters; ++c) {
+            x[c] = *slot(ring, t0 + i, c, lane);
+            x[kCounters + c] = *slot(ring, t0 + i2, c, lane);
+        }
+#pragma unroll
+        for (int c = 0; c < 2 * kCounters; ++c) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) x[c] += __shfl_xor(x[c], off, 64);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < kCounters; ++c) {
+                totals[size_t(i) * kCounters + c] = x[c];
+                totals[size_t(i2) * kCounters + c] = x[kCounters + c];
+            }
+        }
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence_system();
+        __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 int env_int(const char *name, int dflt) {
     const char *s = getenv(name);
     return s ? atoi(s) : dflt;
@@ -1182,7 +1288,22 @@ struct Tuning {
     int look = 8;              // SWARM_LOOKAHEAD: rounds between a batch's read-back point and its end
     int mark_prune = 1;        // SWARM_MARK_PRUNE: sparse-round risers mark only the neighbours they can still
                                // raise (0: every neighbour)
+    // The start of a sparse round and the launches between rounds ("round start"):
+    // The last three are measured and off (DESIGN_LOG.md, r13): the first two within run-to-run noise of
+    // the election at 10M and 1M agents, the third 0.6 ms slower at 10M.
+    int guard_late = 1;        // SWARM_GUARD_LATE: the sparse guard word is a scalar load behind the first stamp
+                               // loads (0: read and waited for in front of them)
+    int clear_inline = 0;      // SWARM_CLEAR_INLINE: the 256-round stamp clear is done by the sparse round before
+                               // it, behind its own stamp loads (0: a memset between the rounds)
+    int skip_init_copy = 0;    // SWARM_SKIP_INIT_COPY: no copies of ids into the leader buffers when rounds 1 and 2
+                               // are dense (round 1 reads ids; the two rounds write every entry of both buffers)
+    int fused_readback = 0;    // SWARM_FUSED_READBACK: a batch's totals and its epoch word from one launch by one
+                               // workgroup (0: k_batch_totals over one wave per round, then k_signal)
     Tuning() {
+        guard_late = env_int("SWARM_GUARD_LATE", 1);
+        clear_inline = env_int("SWARM_CLEAR_INLINE", 0);
+        skip_init_copy = env_int("SWARM_SKIP_INIT_COPY", 0);
+        fused_readback = env_int("SWARM_FUSED_READBACK", 0);
         mark_prune = env_int("SWARM_MARK_PRUNE", 1);
         look = env_int("SWARM_LOOKAHEAD", 8);
         if (look < 1) look = 1;
@@ -1318,6 +1439,7 @@ int frontier_alloc(swarm_ctx *ctx, int64_t n_rows, int64_t n_all, int32_t *L0, i
     ctx->step_c16_esc = false;
     ctx->step_c16_checked = false;
     ctx->step_rd_agent = ctx->step_wr_agent = 0;
+    ctx->step_cleared_for = 0;
     int rc = frontier_bind(ctx, L0, L1, f);
     if (rc) return rc;
     SW_HIP(hipMemsetAsync(f->ring, 0, ring_bytes(), s));
@@ -1339,62 +1461,80 @@ RoundKind plan_round(int t) {
     return RK_SPARSE;
 }
 
+// One k_sparse_block launch: the leading arguments resolved here from the frontier and the round.
+template <typename Off, int S, bool DIR, typename CT, bool PRUNE>
+void launch_sparse(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
+                   const int32_t *hcol, hipStream_t s) {
+    const unsigned grid = grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks));
+    const SparseRest<Off, CT> a{f.L[t & 1], f.act[(t + 1) & 1], f.ring, f.tot, f.n_rows, f.c_lo, f.n_count,
+                                f.sm,       f.wsm,              cols,   hrp,   hcol};
+    const unsigned long long *gw = (guard && t > 2) ? f.tot + (t - 2) % kRing : nullptr;
+    if (!tuning().guard_late) flags |= SF_GUARD_EARLY;
+    hipLaunchKernelGGL((k_sparse_block<Off, S, DIR, CT, kG, kKs, PRUNE>), dim3(grid), dim3(kBlock), 0, s, f.act[t & 1],
+                       gw, static_cast<const int32_t *>(f.L[(t - 1) & 1]), rp, uint32_t(f.sm.M), uint32_t(grid), t,
+                       unsigned(stamp_of(t)) * 0x01010101u, flags, a);
+}
+
 // The sparse round of a symmetric graph: chunk size and column type from the frontier, PRUNE from
 // SWARM_MARK_PRUNE.
 template <typename Off, bool PRUNE>
-int launch_sparse_round(const Off *rp, const int32_t *col, const Frontier &f, int t, int guard, hipStream_t s) {
+int launch_sparse_round(const Off *rp, const int32_t *col, const Frontier &f, int t, int guard, unsigned flags,
+                        hipStream_t s) {
     const bool small = f.sm.cshift == 9;  // small swarm: 512-agent chunks, 4x the workgroups
-    const dim3 grid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
     const Col32 c32{col};
     if (f.c16 && f.c16_esc && small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col16E, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
-                           Col16E{f.c16, col}, f, t, guard, nullptr, nullptr);
+        launch_sparse<Off, 2, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s);
     else if (f.c16 && f.c16_esc)
-        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col16E, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
-                           Col16E{f.c16, col}, f, t, guard, nullptr, nullptr);
+        launch_sparse<Off, kScan, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s);
     else if (f.c16 && small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col16, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
-                           Col16{f.c16}, f, t, guard, nullptr, nullptr);
+        launch_sparse<Off, 2, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s);
     else if (f.c16)
-        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col16, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
-                           Col16{f.c16}, f, t, guard, nullptr, nullptr);
+        launch_sparse<Off, kScan, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s);
     else if (small)
-        hipLaunchKernelGGL((k_sparse_block<Off, 2, false, Col32, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp, c32,
-                           f, t, guard, nullptr, nullptr);
+        launch_sparse<Off, 2, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s);
     else
-        hipLaunchKernelGGL((k_sparse_block<Off, kScan, false, Col32, kG, kKs, PRUNE>), grid, dim3(kBlock), 0, s, rp,
-                           c32, f, t, guard, nullptr, nullptr);
+        launch_sparse<Off, kScan, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s);
     SW_LAUNCHED();
     return SWARM_OK;
 }
 
+// Whether sparse round t clears the buffer it marks into first (parity t+1, last read by round t-1):
+// every 256 rounds, per parity, so no stamp outlives the 510 rounds after which its value recurs
+// (take_stamps).
+bool clear_due(int t) { return t > 2 && ((t - 1) & 255) < 2; }
+
 // hrp/hcol: the transpose CSR of a directed graph (who hears each agent), or NULL (symmetric).
+// cleared_for (optional, kept by the caller across the rounds of one run): the round whose clear the
+// sparse round before it has already done inside its own launch (SF_CLEAR); 0: none.
 template <typename Off>
 int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, int t, RoundKind k, int guard,
-                          hipStream_t s, const Off *hrp = nullptr, const int32_t *hcol = nullptr) {
+                          hipStream_t s, const Off *hrp = nullptr, const int32_t *hcol = nullptr,
+                          int *cleared_for = nullptr) {
     if (k == RK_DENSE || k == RK_DENSE_MARK)
         return launch_dense_round<Off>(rp, col, f.L[(t - 1) & 1], f.L[t & 1], f.n_rows, f.c_lo, f.n_count, f.ring,
                                        f.tot,
                                        k == RK_DENSE_MARK ? f.act[(t + 1) & 1] : nullptr, f.wsm, t, guard, s, hrp,
                                        hcol, f.c16_esc ? nullptr : f.c16);  // escapes: dense rounds read int32
-    // the buffer this round marks into (parity t+1) was read by round t-1; every 256 rounds, per
-    // parity, it is cleared first, so no stamp outlives the 510 rounds after which its value
-    // recurs (take_stamps)
-    if (t > 2 && ((t - 1) & 255) < 2) SW_HIP(hipMemsetAsync(f.act[(t + 1) & 1], 0, act_bytes(f.n_all), s));
+    // The clear: done by round t-1 where that was a sparse round launched here with SF_CLEAR (it zeroed
+    // every stamp word behind its load), by a memset otherwise -- after a dense round, the one-workgroup
+    // tail, or at the first round of a stepper run.
+    if (clear_due(t) && !(cleared_for && *cleared_for == t))
+        SW_HIP(hipMemsetAsync(f.act[(t + 1) & 1], 0, act_bytes(f.n_all), s));
+    unsigned flags = 0;
+    if (tuning().clear_inline && cleared_for && clear_due(t + 1)) {  // this round is that buffer's last reader
+        flags |= SF_CLEAR;
+        *cleared_for = t + 1;
+    }
     if (hrp) {  // directed: the marks go to hearers, whose leaders the riser did not read -- never pruned
-        const bool small = f.sm.cshift == 9;
-        const dim3 grid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
-        if (small)
-            hipLaunchKernelGGL((k_sparse_block<Off, 2, true>), grid, dim3(kBlock), 0, s, rp, Col32{col}, f, t, guard,
-                               hrp, hcol);
+        if (f.sm.cshift == 9)
+            launch_sparse<Off, 2, true, Col32, false>(rp, Col32{col}, f, t, guard, flags, hrp, hcol, s);
         else
-            hipLaunchKernelGGL((k_sparse_block<Off, kScan, true>), grid, dim3(kBlock), 0, s, rp, Col32{col}, f, t,
-                               guard, hrp, hcol);
+            launch_sparse<Off, kScan, true, Col32, false>(rp, Col32{col}, f, t, guard, flags, hrp, hcol, s);
         SW_LAUNCHED();
         return SWARM_OK;
     }
-    return tuning().mark_prune ? launch_sparse_round<Off, true>(rp, col, f, t, guard, s)
-                               : launch_sparse_round<Off, false>(rp, col, f, t, guard, s);
+    return tuning().mark_prune ? launch_sparse_round<Off, true>(rp, col, f, t, guard, flags, s)
+                               : launch_sparse_round<Off, false>(rp, col, f, t, guard, flags, s);
 }
 
 // Algorithmic HBM bytes of one round:
@@ -1518,11 +1658,17 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
     }
     int32_t *bufs[2] = {leader, nullptr};
     SW_ALLOC(bufs[1], ctx, S_LEADER_B, size_t(n) * 4);
-    SW_HIP(hipMemcpyAsync(leader, ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
+    // The leader buffers start as copies of ids -- unless rounds 1 and 2 are both dense: round 1 then reads
+    // ids itself and writes every entry of bufs[1], round 2 every entry of bufs[0] = leader, and no later
+    // round reads anything older.  A call whose ids overlaps leader keeps the copies.
+    const bool aliased = ids < leader + n && leader < ids + n;
+    const bool skip_copy = tuning().skip_init_copy && !aliased &&
+                           (mode == SWARM_ELECT_DENSE || tuning().dense_rounds >= 2);
+    if (!skip_copy) SW_HIP(hipMemcpyAsync(leader, ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
     Frontier f{};
     unsigned long long *ring;
     if (mode == SWARM_ELECT_FRONTIER) {
-        SW_HIP(hipMemcpyAsync(bufs[1], ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
+        if (!skip_copy) SW_HIP(hipMemcpyAsync(bufs[1], ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
         int rc0 = frontier_alloc(ctx, n, n, bufs[0], bufs[1], &f, s);
         if (rc0) return rc0;
         ring = f.ring;
@@ -1610,16 +1756,29 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         read_upto = tread;
     };
     // the counters of rounds (read_upto, upto] read back and consumed (every launched round drained)
-    auto read_rounds = [&](int upto) -> int {
-        if (upto <= read_upto) return SWARM_OK;
+    // per-round totals of rounds (read_upto, upto], reduced on device into mapped host memory, then the
+    // batch's epoch word: one launch (SWARM_FUSED_READBACK) or two
+    auto enqueue_totals = [&](int upto) -> int {
+        if (tuning().fused_readback) {
+            hipLaunchKernelGGL(k_batch_totals_signal, dim3(1), dim3(kReadbackThreads), 0, s, ring, read_upto + 1,
+                               upto - read_upto, dtot, d_epoch, ep_tag | ++ep);
+            SW_LAUNCHED();
+            return SWARM_OK;
+        }
         hipLaunchKernelGGL(k_batch_totals, dim3(upto - read_upto), dim3(kWave), 0, s, ring, read_upto + 1, dtot);
         SW_LAUNCHED();
         hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, s, d_epoch, ep_tag | ++ep);
         SW_LAUNCHED();
+        return SWARM_OK;
+    };
+    auto read_rounds = [&](int upto) -> int {
+        if (upto <= read_upto) return SWARM_OK;
+        if (int rc2 = enqueue_totals(upto)) return rc2;
         if (int rc2 = wait_mapped_word(h_epoch, ep_tag | ep, s, "election read-back")) return rc2;
         consume(upto);
         return SWARM_OK;
     };
+    int cleared_for = 0;  // the round whose stamp clear the round before it did in its own launch
     int64_t tail_retry_below = INT64_MAX;  // the tail did not start: retry once the changes halve
     // One-workgroup tail from round launched + 1: drain, collect the marked agents, run k_tail_wg, read its
     // rounds' counters.  Leaves launched / rd_map where the frontier rounds go on.
@@ -1688,15 +1847,7 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         // read rounds (read_upto, tread]: at least one (the first batches are shorter than kLook)
         const int tread = tend == max_rounds ? tend : std::max(read_upto + 1, tend - kLook);
         int rc = 0;
-        // per-round totals of rounds (read_upto, tread], reduced on device into mapped host memory, then
-        // the batch's epoch word
-        auto enqueue_read = [&]() -> int {
-            hipLaunchKernelGGL(k_batch_totals, dim3(tread - read_upto), dim3(kWave), 0, s, ring, read_upto + 1, dtot);
-            SW_LAUNCHED();
-            hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, s, d_epoch, ep_tag | ++ep);
-            SW_LAUNCHED();
-            return SWARM_OK;
-        };
+        auto enqueue_read = [&]() -> int { return enqueue_totals(tread); };
         if (tread <= launched && (rc = enqueue_read())) return rc;
         // timing: dense rounds (and every round when a per-round log is written) get an event pair
         // each; a batch's run of back-to-back sparse rounds gets ONE pair around it -- events
@@ -1711,15 +1862,21 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
             if (e2) SW_HIP(hipEventRecord(e2[0], s));
             if (mode == SWARM_ELECT_DENSE) {
                 kinds[r - t] = RK_DENSE;
-                rc = launch_dense_round<Off>(rp, col, bufs[(r - 1) & 1], bufs[r & 1], n, 0, n, ring, nullptr, nullptr,
-                                             StampMap{}, r, 1, s, nullptr, nullptr, c16);
+                rc = launch_dense_round<Off>(rp, col, (r == 1 && skip_copy) ? ids : bufs[(r - 1) & 1], bufs[r & 1], n, 0,
+                                             n, ring, nullptr, nullptr, StampMap{}, r, 1, s, nullptr, nullptr, c16);
+            } else if (r == 1 && skip_copy) {  // a dense round (dense_rounds >= 2) that reads ids
+                kinds[r - t] = plan_round(r);
+                Frontier f1 = f;
+                f1.L[0] = const_cast<int32_t *>(ids);
+                f1.sm = f1.wsm = il_map;
+                rc = launch_frontier_round<Off>(rp, col, f1, r, kinds[r - t], 1, s, hrp, hcol);
             } else {
                 kinds[r - t] = plan_round(r);
                 // marks for round r+1: interleaved layout while rounds are busy (balance), agent
                 // order once they are sparse (locality of the few gathers)
                 f.sm = rd_map;
                 f.wsm = (hist.empty() || hist.back() >= il_min) ? il_map : ag_map;
-                rc = launch_frontier_round<Off>(rp, col, f, r, kinds[r - t], 1, s, hrp, hcol);
+                rc = launch_frontier_round<Off>(rp, col, f, r, kinds[r - t], 1, s, hrp, hcol, &cleared_for);
                 rd_map = f.wsm;
             }
             if (rc) return rc;
@@ -1769,9 +1926,10 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         }
     }
     const int last = found > 0 ? found : max_rounds;
-    if (found < 0 && (last & 1)) {
+    if ((found < 0 && (last & 1)) || (skip_copy && last == 1)) {
         // after a zero-change round both buffers hold the final state (dense and frontier alike);
-        // otherwise the newest is bufs[last & 1]
+        // otherwise the newest is bufs[last & 1].  (Without the initial copies a run that ends with
+        // round 1 has written bufs[1] only, zero changes or not.)
         SW_HIP(hipMemcpyAsync(leader, bufs[1], size_t(n) * 4, hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(k_state, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, leader,
@@ -1825,7 +1983,8 @@ int frontier_round_stepper(swarm_ctx *ctx, int t, const int32_t *rp, const int32
     if (rc) return rc;
     if (f.n_rows == 0) return SWARM_OK;
     if ((rc = frontier_check_compact(ctx, rp, col, s))) return rc;
-    rc = launch_frontier_round<int32_t>(rp, col, f, t, plan_round(t), /*guard=*/0, s);
+    rc = launch_frontier_round<int32_t>(rp, col, f, t, plan_round(t), /*guard=*/0, s, nullptr, nullptr,
+                                        &ctx->step_cleared_for);
     ctx->step_rd_agent = ctx->step_wr_agent;  // the marks this round wrote
     return rc;
 }

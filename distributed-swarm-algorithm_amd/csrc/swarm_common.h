@@ -113,6 +113,7 @@ struct swarm_ctx {
     std::vector<C16Built> c16_built;
     int step_rd_agent = 0;         // frontier stepper: the marks the next round reads are in agent order
     int step_wr_agent = 0;         // ... and the next round writes its marks in agent order (the tail)
+    int step_cleared_for = 0;      // frontier stepper: the round whose stamp clear the round before it has done
     hipStream_t side = nullptr;    // a second stream for work that overlaps the caller's (side_stream)
     hipEvent_t side_ev[2] = {};    // fork / join events
     void *enc_flags = nullptr;     // codec one-pass encode: the S_ENC_FLAGS buffer last zeroed ...
