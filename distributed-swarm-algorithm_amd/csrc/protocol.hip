@@ -43,14 +43,17 @@
 // refused tick makes the call restore every caller array on the device (k_restore_refused: all or nothing).
 // swarm_update_loop_radio (U1-R) is the sensed loop without a message graph: k_tick_radio is k_tick_pull's
 // agent with the row walk replaced by the merge over its 3 x 3 cell window of the same binning.
-// The host loop of all five entry points is run_ticks, a sequence of stages that each own their scratch:
-// check_run_args, Counters, pack_records, PushState / RadioState / launch_tick_pull (the receive launch by
+// swarm_update_loop_tasks (U1-T) is the radio loop with _process_tasks and the two task handlers run every tick:
+// k_radio_outbox_tasks, k_task_conflicts and k_tick_radio_tasks in place of the two radio kernels (TaskState).
+// The host loop of all six entry points is run_ticks, a sequence of stages that each own their scratch:
+// check_run_args, Counters, pack_records, PushState / RadioState / TaskState / launch_tick_pull (the receive launch by
 // mode), EntrySnapshot (sensed), TickClocks (A/B aid), tick_physics, read_back (one host wait).
 #include <cmath>
 #include <cstring>
 
 #include "fsm_records.h"
 #include "tick_segments.h"
+#include "utility.h"
 #include "window_merge.h"
 
 namespace swarm {
@@ -1001,6 +1004,358 @@ __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, con
     add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
 }
 
+// ---------------------------------------------------------------- task update loop (contract U1-T)
+// U1-R's tick with _process_tasks and the two task handlers (agent.py:292-336), DESIGN 4i.  Per agent: a
+// 2-bit status per task (two 64-bit words), its claim table (a dense row of T winners and f32 utilities), and
+// by tick parity the set of tasks it claimed and the set it sent a TASK_CONFLICT on.  Three launches per tick,
+// none of them U1-R's kernels (those keep their instructions):
+//   k_radio_outbox_tasks  k_radio_outbox with two more bits in the cell-sorted byte -- the sender claimed, the
+//                         sender sent a conflict -- and a cell byte for each of the three kinds of sender; it
+//                         gathers one scratch byte per agent (TaskTick::sb_in), which the tick kernel wrote;
+//   k_task_conflicts      the tick's TASK_CONFLICT delivery, before the receive: it writes only the status,
+//                         which only the logic step reads, so it commutes with the rest of the receive; and one
+//                         bit per (sender, task) is its whole outbox, because the last conflict a leader sent on
+//                         a task names the winner its table holds at the end of that tick's receive -- read
+//                         here from the sender's row, which no thread of this launch writes;
+//   k_tick_radio_tasks    k_tick_radio's agent with the claims of each heard sender handled right after its
+//                         election packets (LEADERs only, on all three paths), then the timers, then the claim
+//                         evaluation of the tasks still OPEN against the board staged in LDS.
+// A receiver that is not LEADER at the start of the tick never handles a claim (hear() only ever leaves
+// FOLLOWER behind), so it ignores the claim bits and the claim cells: a claimer costs the followers around it
+// nothing.
+constexpr uint8_t kClaim = 4, kConflict = 8;
+constexpr int kMaxTasks = 64;
+constexpr double kClaimThr = 20.0, kHysteresis = 5.0, kUScale = 100.0;
+// An OPEN task further than this (squared) is never claimed and never in the guard band: d2 > 25 gives
+// sqrt(d2) >= 5 (IEEE sqrt is monotone and sqrt(25) = 5 exactly), so U <= fl(100 / 6) < 17 -- the same d2 the
+// utility would take the root of (fp-contract off), so the skip is exact, NaN included (!(NaN <= 25): no
+// claim, no guard, as utility() and guard_flag() give).
+constexpr double kClaimFar2 = 25.0;
+
+struct TaskTick {
+    int32_t T;
+    unsigned long long tmask;  // bits 0 .. T-1: a bit past the board in a caller's word is never an index
+    const double2 *tpos;
+    const int8_t *treq;
+    const uint32_t *caps;
+    unsigned long long *status_lo, *status_hi;
+    const unsigned long long *claim_in, *conflict_in;  // tick t-1's sets
+    unsigned long long *claim_out, *conflict_out;      // tick t's
+    int32_t *tab_winner;
+    float *tab_util;
+    uint8_t *cell_claim, *cell_conf;  // as Radio::cell_send: the cell holds a claimer / a conflict sender
+    unsigned long long *cnt;          // the tick's kShards x 4: claims sent, handled, conflicts sent, guard pairs
+    // The sender bytes (scratch, by tick parity like the outbox): the outbox bits plus kClaim / kConflict when the
+    // agent's claim / conflict word of that tick is not empty.  A quiet agent then costs a byte each way instead
+    // of its four 64-bit words: the outbox pass gathers this byte alone, and the tick kernel rewrites a word only
+    // when it, or the word of two ticks ago in the same slot, holds something.
+    const uint8_t *sb_in;  // tick t-1's
+    uint8_t *sb_out;       // in: tick t-2's, out: tick t's
+};
+
+// The sender bytes of both parities from the caller's outbox and words (once per call).
+__global__ __launch_bounds__(kBlock) void k_task_sender_bytes(int64_t n2, const uint8_t *__restrict__ ob,
+                                                             const unsigned long long *__restrict__ claim,
+                                                             const unsigned long long *__restrict__ conflict,
+                                                             unsigned long long tmask, uint8_t *__restrict__ sb) {
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n2; q += int64_t(gridDim.x) * kBlock)
+        sb[q] = uint8_t((ob[q] & (kAcclaim | kHeartbeat)) | ((claim[q] & tmask) ? kClaim : 0) |
+                        ((conflict[q] & tmask) ? kConflict : 0));
+}
+
+__global__ __launch_bounds__(kBlock) void k_radio_outbox_tasks(int64_t n, Radio w, TaskTick k) {
+    if (w.st[0] != 0) return;
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n; q += int64_t(gridDim.x) * kBlock) {
+        const uint8_t o = k.sb_in[w.sorted[q]];
+        const uint8_t fsm = o & (kAcclaim | kHeartbeat);
+        const bool cl = (o & kClaim) != 0, cf = (o & kConflict) != 0;
+        w.ob_sorted[q] = o;
+        if (o) {  // (every writer of a cell's byte stores the same 1)
+            const double2 p = w.psort[q];
+            const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+            const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+            const int64_t c = cy * w.g.ncx + cx;
+            if (fsm) w.cell_send[c] = 1;
+            if (cl) k.cell_claim[c] = 1;
+            if (cf) k.cell_conf[c] = 1;
+        }
+    }
+}
+
+// _handle_task_conflict (327-336) for every alive agent, over the conflict senders it hears, in ascending
+// storage index; within a sender ascending task (one message per task is all that matters: the last).
+__global__ __launch_bounds__(kBlock) void k_task_conflicts(int64_t n, const int32_t *__restrict__ ids,
+                                                          const uint2 *__restrict__ rec, Radio w, TaskTick k) {
+    if (w.st[0] != 0) return;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const double2 p = w.psort[q0];
+        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+        uint8_t any = 0;  // the nine bytes loaded at once
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const int64_t yy = cy + (c / 3) - 1, xx = cx + (c % 3) - 1;
+            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
+            const uint8_t fl = k.cell_conf[in ? yy * w.g.ncx + xx : 0];
+            any |= in ? fl : uint8_t(0);
+        }
+        if (!any) continue;
+        const int64_t i = w.sorted[q0];
+        if (!fw_alive(rec[i].x)) continue;
+        const int32_t me = ids[i];
+        const unsigned long long lo0 = k.status_lo[i], hi0 = k.status_hi[i];
+        unsigned long long lo = lo0, hi = hi0;
+        window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
+            if (!(w.ob_sorted[q] & kConflict) || j == int32_t(i)) return;
+            const double2 s = w.psort[q];
+            const double ex = p.x - s.x, ey = p.y - s.y;
+            if (!(ex * ex + ey * ey <= w.r2)) return;
+            unsigned long long m = k.conflict_in[j] & k.tmask;
+            const int32_t *row = k.tab_winner + int64_t(j) * k.T;
+            while (m) {
+                const int t = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const unsigned long long bit = 1ull << t;
+                hi |= bit;  // ASSIGNED (3) for the winner, LOCKED (2) for everyone else
+                lo = row[t] == me ? lo | bit : lo & ~bit;
+            }
+        });
+        if (lo != lo0) k.status_lo[i] = lo;
+        if (hi != hi0) k.status_hi[i] = hi;
+    }
+}
+
+// _handle_task_claim (304-325) at a LEADER, for the claims sender j (ID sid) sent during tick t-1: its
+// utilities recomputed from the position it claimed at (the lagged buffer) -- the same function of the same
+// operands as its own evaluation, bit for bit -- and rounded to the '!f' payload.
+struct ClaimRx {
+    const unsigned long long *claim_in;
+    const double2 *lag;
+    const uint32_t *caps;
+    int32_t *tw;  // the receiver's table row
+    float *tu;
+    const double *tx, *ty;  // the board (LDS)
+    const int8_t *rq;
+    unsigned long long conf;  // tasks it sent a conflict on during this tick
+    unsigned handled, sent;
+    unsigned long long tmask;
+};
+
+__device__ __forceinline__ void hear_claims(ClaimRx &c, int32_t j, int32_t sid) {
+    unsigned long long m = c.claim_in[j] & c.tmask;
+    if (!m) return;
+    const double2 a = c.lag[j];
+    const uint32_t cp = c.caps[j];
+    while (m) {
+        const int t = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const float u = float(utility(a.x, a.y, cp, c.tx[t], c.ty[t], c.rq[t], kUScale));
+        const int32_t hw = c.tw[t];
+        const float hu = c.tu[t];
+        ++c.handled;
+        if (hw < 0 || double(u) > double(hu) + kHysteresis) {
+            c.tw[t] = sid;
+            c.tu[t] = u;
+            c.conf |= 1ull << t;
+            ++c.sent;
+        } else if (hw != sid) {  // re-affirm the held winner
+            c.conf |= 1ull << t;
+            ++c.sent;
+        }
+    }
+}
+
+// The tasks that can be within reach of any lane of the wave (bit k: task k), for all 64 lanes at once: the
+// wave's bounding box by shuffles, then lane k judges task k against it.  The box is reduced in f32 (half the
+// shuffles) and widened by what the rounding to f32 can have lost, sx >= |x| 2^-24 for every x of the wave.  A
+// task is left out only when it lies more than kWaveFar + sx beyond the box on some axis: then for every lane
+// tx - x >= tx - xmax > 5.5, so fl(x - tx) < -5.4, its dx * dx > 29 and the far pre-test would skip the task
+// anyway -- the mask never changes a result.  Lanes without an agent and non-finite agents pass NaN: fminf /
+// fmaxf ignore them, and a NaN agent fails every pre-test by itself.  A wave of NaNs, or one with an agent
+// beyond f32's range, keeps every task (the comparisons are false).
+constexpr double kWaveFar = 5.5;
+constexpr double kNaN = __builtin_nan("");
+static_assert(kWave == 64 && kMaxTasks <= kWave, "one lane per task");
+__device__ __forceinline__ unsigned long long wave_tasks(double2 p, int T, const double *s_tx, const double *s_ty) {
+    float x0 = float(p.x), x1 = x0, y0 = float(p.y), y1 = y0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        x0 = fminf(x0, __shfl_xor(x0, off, 64));
+        x1 = fmaxf(x1, __shfl_xor(x1, off, 64));
+        y0 = fminf(y0, __shfl_xor(y0, off, 64));
+        y1 = fmaxf(y1, __shfl_xor(y1, off, 64));
+    }
+    const int l = threadIdx.x & (kWave - 1);
+    bool keep = false;
+    if (l < T) {
+        const double tx = s_tx[l], ty = s_ty[l];
+        const double fx = kWaveFar + fmax(fabs(double(x0)), fabs(double(x1))) * 0x1p-23;
+        const double fy = kWaveFar + fmax(fabs(double(y0)), fabs(double(y1))) * 0x1p-23;
+        keep = !(tx - double(x1) > fx || double(x0) - tx > fx || ty - double(y1) > fy || double(y0) - ty > fy);
+    }
+    return __ballot(keep);
+}
+
+// At >= 4 waves per SIMD (128 VGPRs, none spilled): leg (a) of tools/bench_loop_tasks.py 4.28-4.30 ms per tick
+// against 4.44-4.46 at the compiler's 3 (138 VGPRs), same session; 5 waves would need scratch (38 VGPRs spilled).
+__global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64_t t, const int32_t *__restrict__ ids,
+                                                            const double2 *__restrict__ pos, Fsm f, Radio w,
+                                                            uint8_t *__restrict__ ob_out, double dt, double timeout,
+                                                            double jitter, uint64_t seed,
+                                                            unsigned long long *__restrict__ counts, TaskTick k) {
+    __shared__ unsigned s_cnt[4], s_tcnt[4];
+    __shared__ double s_tx[kMaxTasks], s_ty[kMaxTasks];
+    __shared__ int8_t s_rq[kMaxTasks];
+    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = s_tcnt[threadIdx.x] = 0;
+    if (int(threadIdx.x) < k.T) {
+        const double2 q = k.tpos[threadIdx.x];
+        s_tx[threadIdx.x] = q.x;
+        s_ty[threadIdx.x] = q.y;
+        s_rq[threadIdx.x] = k.treq[threadIdx.x];
+    }
+    __syncthreads();
+    const double now = double(t) * dt;
+    unsigned c_lead = 0, c_wait = 0, c_acc = 0, c_hb = 0, c_claim = 0, c_guard = 0;
+    ClaimRx cr{k.claim_in, pos, k.caps, nullptr, nullptr, s_tx, s_ty, s_rq, 0ull, 0u, 0u, k.tmask};
+    // (the trip count is uniform over the workgroup: every wave enters wave_tasks with all its lanes)
+    for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
+        const int64_t q0 = base + threadIdx.x;
+        const bool valid = q0 < n;
+        const double2 p = valid ? w.psort[q0] : make_double2(kNaN, kNaN);
+        const unsigned long long reach = wave_tasks(p, k.T, s_tx, s_ty);
+        if (!valid) continue;
+        const int64_t i = w.sorted[q0];
+        const uint2 r = f.rec[i];
+        const uint32_t fw = r.x;
+        const uint8_t old = k.sb_out[i];  // what this slot's words hold (tick t-2's sends)
+        if (!fw_alive(fw)) {
+            ob_out[i] = 0;
+            if (old & kClaim) k.claim_out[i] = 0;
+            if (old & kConflict) k.conflict_out[i] = 0;
+            if (old) k.sb_out[i] = 0;
+            continue;
+        }
+        const int32_t me = ids[i];
+        const uint8_t st0 = fw_state(fw);
+        const int32_t ph = fw_phase(fw);
+        const bool hb_tick = ((t + ph) % 10) == 0;
+        uint32_t bits = fw_bits(fw);
+        int32_t y = int32_t(r.y);
+        Heard h{st0, 0, false, false, 0, -1};
+        // only a LEADER's walk looks at claims (see the header)
+        const bool lead0 = st0 == ST_L;
+        const uint8_t rel = uint8_t(kAcclaim | kHeartbeat | (lead0 ? kClaim : 0));
+        cr.tw = k.tab_winner + i * k.T;
+        cr.tu = k.tab_util + i * k.T;
+        cr.conf = 0;
+        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+        unsigned cells = 0;  // bit c: window cell c holds a sender this receiver listens to
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const int64_t yy = cy + (c / 3) - 1, xx = cx + (c % 3) - 1;
+            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
+            const int64_t at = in ? yy * w.g.ncx + xx : 0;
+            uint8_t fl = w.cell_send[at];
+            if (lead0) fl |= k.cell_claim[at];
+            cells |= in && fl ? 1u << c : 0u;
+        }
+        const bool crowded = __popc(cells) > kHeardCells;
+        if (cells) {
+            int32_t sj[kHeardFast];
+            uint8_t so[kHeardFast];
+#pragma unroll
+            for (int u = 0; u < kHeardFast; ++u) {
+                sj[u] = kMergeEnd;
+                so[u] = 0;
+            }
+            bool more = crowded;
+            for (int c = 0; c < 9 && !crowded; ++c) {
+                if (!((cells >> c) & 1u)) continue;
+                const int64_t cell = (cy + (c / 3) - 1) * w.g.ncx + cx + (c % 3) - 1;
+                for (uint32_t q = w.off[cell], e = w.off[cell + 1]; q < e; ++q) {
+                    uint8_t o = w.ob_sorted[q] & rel;
+                    if (!o) continue;
+                    int32_t j = w.sorted[q];
+                    const double2 s = w.psort[q];
+                    const double ex = p.x - s.x, ey = p.y - s.y;
+                    if (j == int32_t(i) || !(ex * ex + ey * ey <= w.r2)) continue;
+#pragma unroll
+                    for (int u = 0; u < kHeardFast; ++u) {
+                        const bool lower = j < sj[u];
+                        const int32_t tj = sj[u];
+                        const uint8_t to = so[u];
+                        sj[u] = lower ? j : tj;
+                        so[u] = lower ? o : to;
+                        j = lower ? tj : j;
+                        o = lower ? to : o;
+                    }
+                    more |= j != kMergeEnd;  // an index fell off the end of the list
+                }
+            }
+            if (!more) {
+                int32_t ss[kHeardFast];  // the senders' IDs, all loads in flight
+#pragma unroll
+                for (int u = 0; u < kHeardFast; ++u) ss[u] = sj[u] != kMergeEnd ? ids[sj[u]] : 0;
+#pragma unroll
+                for (int u = 0; u < kHeardFast; ++u) {
+                    if (sj[u] == kMergeEnd) continue;
+                    hear(h, so[u], ss[u], sj[u], me, hb_tick);
+                    if ((so[u] & kClaim) && h.st == ST_L) hear_claims(cr, sj[u], ss[u]);
+                }
+            } else {
+                window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
+                    const uint8_t o = w.ob_sorted[q] & rel;
+                    if (!o || j == int32_t(i)) return;
+                    const double2 s = w.psort[q];
+                    const double ex = p.x - s.x, ey = p.y - s.y;
+                    if (!(ex * ex + ey * ey <= w.r2)) return;
+                    const int32_t sid = ids[j];
+                    hear(h, o, sid, j, me, hb_tick);
+                    if ((o & kClaim) && h.st == ST_L) hear_claims(cr, j, sid);
+                });
+            }
+        }
+        apply_heard(i, h, t, pos, f, bits, y);
+        const uint8_t ob = h.ob | timers(i, h.st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
+                                         ph, f, bits, y);
+        const uint32_t fw1 = fw_make(h.st, 1, bits, ph);
+        if (fw1 != fw || uint32_t(y) != r.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
+        if (h.lead_set) f.lrec[i].leader = h.lead;
+        ob_out[i] = ob;
+        c_lead += h.st == ST_L;
+        c_wait += h.st == ST_W;
+        c_acc += (ob & kAcclaim) != 0;
+        c_hb += (ob & kHeartbeat) != 0;
+        // _process_tasks (292-302): the tasks still OPEN after this tick's conflicts, at the tick's snapshot;
+        // the status is read only when a task is near the wave at all
+        unsigned long long claims = 0;
+        if (reach) {
+            const unsigned long long lo = k.status_lo[i];
+            unsigned long long open = ~(lo | k.status_hi[i]) & reach;
+            const uint32_t cp = k.caps[i];
+            while (open) {
+                const int c = __ffsll((long long)open) - 1;
+                open &= open - 1;
+                const double dx = p.x - s_tx[c], dy = p.y - s_ty[c];
+                if (!(dx * dx + dy * dy <= kClaimFar2)) continue;
+                const double U = utility(p.x, p.y, cp, s_tx[c], s_ty[c], s_rq[c], kUScale);
+                c_guard += guard_flag(U, kClaimThr);
+                if (U > kClaimThr) claims |= 1ull << c;
+            }
+            if (claims) k.status_lo[i] = lo | claims;  // TENTATIVE
+        }
+        if (claims || (old & kClaim)) k.claim_out[i] = claims;
+        if (cr.conf || (old & kConflict)) k.conflict_out[i] = cr.conf;
+        const uint8_t sent = uint8_t(ob | (claims ? kClaim : 0) | (cr.conf ? kConflict : 0));
+        if (sent != old) k.sb_out[i] = sent;
+        c_claim += unsigned(__popcll(claims));
+    }
+    add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
+    add_counts(c_claim, cr.handled, cr.sent, c_guard, s_tcnt, k.cnt);
+}
+
 // ---------------------------------------------------------------- the host loop, in stages
 // One run's arguments, as the five entry points fill them (`loop`: swarm_update_loop*, each tick then followed
 // by its physics step; `pos` is not used then, the heartbeats read the lagged buffer).
@@ -1021,6 +1376,9 @@ struct TickRun {
     int64_t *counts, *traffic;
     const LoopArgs *loop;
     void *stream;
+    const swarm_tasks *tasks = nullptr;  // U1-T (T > 0: swarm_update_loop_tasks), with its two host outputs
+    int64_t *task_counts = nullptr, *n_guard = nullptr;
+    bool tasked() const { return tasks && tasks->T > 0; }
     bool sensed() const { return loop && loop->sense_radius > 0.0; }
     bool radio() const { return loop && loop->radio_radius > 0.0; }
     bool push() const { return hear_row_ptr != nullptr; }
@@ -1164,13 +1522,14 @@ struct RadioState {
     Radio rw{};
     size_t cells = 0;
 
-    int begin(const TickRun &r, const LoopSense &ls) {
+    // planes: bytes per cell (U1-T keeps one for each kind of sender, TaskState)
+    int begin(const TickRun &r, const LoopSense &ls, int planes = 1) {
         rw.g = ls.g;
         rw.r2 = r.loop->radio_radius * r.loop->radio_radius;
         rw.st = ls.st;
         cells = size_t(ls.g.ncx * ls.g.ncy);
         SW_ALLOC(rw.ob_sorted, r.ctx, S_RADIO_OUTBOX, size_t(r.n));
-        SW_ALLOC(rw.cell_send, r.ctx, S_RADIO_CELLS, cells);
+        SW_ALLOC(rw.cell_send, r.ctx, S_RADIO_CELLS, cells * size_t(planes));
         return SWARM_OK;
     }
 
@@ -1184,6 +1543,66 @@ struct RadioState {
         SW_LAUNCHED();
         hipLaunchKernelGGL(k_tick_radio, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
                            r.timeout, r.jitter, r.seed, k.cnt);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+};
+
+// Task mode (U1-T): RadioState's scratch with three bytes per cell, the per-tick task counters (sharded as the
+// tick counts, the fourth the guard pairs) and the tick's three launches.
+struct TaskState {
+    unsigned long long *part = nullptr, *sums = nullptr;
+    uint8_t *sb = nullptr;  // the sender bytes, 2n by tick parity (TaskTick)
+    unsigned long long tmask = 0;
+
+    int begin(const TickRun &r, hipStream_t s) {
+        const size_t ticks = size_t(r.ticks), part_bytes = ticks * kShards * 4 * 8;
+        const swarm_tasks &b = *r.tasks;
+        SW_ALLOC(part, r.ctx, S_TASK_COUNTS, part_bytes + ticks * 4 * 8);
+        sums = part + ticks * kShards * 4;
+        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
+        SW_ALLOC(sb, r.ctx, S_TASK_SENDERS, size_t(r.n) * 2);
+        tmask = b.T >= 64 ? ~0ull : (1ull << b.T) - 1ull;
+        hipLaunchKernelGGL(k_task_sender_bytes, dim3(grid_for(2 * r.n, kBlock, 8192)), dim3(kBlock), 0, s, 2 * r.n,
+                           r.fsm->outbox, reinterpret_cast<const unsigned long long *>(b.claim_out),
+                           reinterpret_cast<const unsigned long long *>(b.conflict_out), tmask, sb);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, RadioState &rs, hipStream_t s) {
+        const dim3 grid(grid_for(r.n, kBlock, 8192));
+        const swarm_tasks &b = *r.tasks;
+        const size_t un = size_t(r.n), in = size_t((k.t - 1) & 1) * un, out = size_t(k.t & 1) * un;
+        auto u64 = [](uint64_t *p) { return reinterpret_cast<unsigned long long *>(p); };
+        rs.rw.sorted = ls.sorted;
+        rs.rw.off = ls.off;
+        rs.rw.psort = ls.psort;
+        const TaskTick tk{b.T,
+                          tmask,
+                          reinterpret_cast<const double2 *>(b.tpos),
+                          b.treq,
+                          b.caps,
+                          u64(b.status_lo),
+                          u64(b.status_hi),
+                          u64(b.claim_out) + in,
+                          u64(b.conflict_out) + in,
+                          u64(b.claim_out) + out,
+                          u64(b.conflict_out) + out,
+                          b.tab_winner,
+                          b.tab_util,
+                          rs.rw.cell_send + rs.cells,
+                          rs.rw.cell_send + 2 * rs.cells,
+                          part + size_t(k.t - r.t0 - 1) * kShards * 4,
+                          sb + in,
+                          sb + out};
+        SW_HIP(hipMemsetAsync(rs.rw.cell_send, 0, 3 * rs.cells, s));
+        hipLaunchKernelGGL(k_radio_outbox_tasks, grid, dim3(kBlock), 0, s, r.n, rs.rw, tk);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_task_conflicts, grid, dim3(kBlock), 0, s, r.n, r.ids, f.rec, rs.rw, tk);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_tick_radio_tasks, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw, k.ob_out,
+                           r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk);
         SW_LAUNCHED();
         return SWARM_OK;
     }
@@ -1203,7 +1622,8 @@ struct EntrySnapshot {
     struct Kept {
         void *p;
         size_t bytes, at;
-    } kept[14];
+    } kept[20];
+    int nkept = 0;
     uint8_t *snap = nullptr;
 
     int take(const TickRun &r, hipStream_t s) {
@@ -1215,21 +1635,30 @@ struct EntrySnapshot {
                               {fsm->delay, un * 8, 0},       {fsm->leader_pos, un * 8, 0},  {fsm->leader, un * 4, 0},
                               {fsm->outbox, un * 2, 0},      {loop->has_target, un, 0},     {fsm->state, un, 0},
                               {fsm->alive, un, 0},           {fsm->has_leader_pos, un, 0}};
+        nkept = 0;
+        for (int q = 0; q < 14; ++q) kept[nkept++] = all[q];
+        if (r.tasked()) {  // U1-T: every task array as well
+            const swarm_tasks &b = *r.tasks;
+            const size_t row = un * size_t(b.T) * 4;
+            const Kept more[6] = {{b.status_lo, un * 8, 0},     {b.status_hi, un * 8, 0}, {b.claim_out, un * 16, 0},
+                                  {b.conflict_out, un * 16, 0}, {b.tab_winner, row, 0},   {b.tab_util, row, 0}};
+            for (int q = 0; q < 6; ++q) kept[nkept++] = more[q];
+        }
         size_t total = 0;
-        for (int q = 0; q < 14; ++q) {
-            kept[q] = all[q];
+        for (int q = 0; q < nkept; ++q) {
             kept[q].at = total;
-            total += (all[q].bytes + 15) & ~size_t(15);
+            total += (kept[q].bytes + 15) & ~size_t(15);
         }
         SW_ALLOC(snap, r.ctx, S_LOOP_SNAP, total);
-        for (const Kept &k : kept)
-            SW_HIP(hipMemcpyAsync(snap + k.at, k.p, k.bytes, hipMemcpyDeviceToDevice, s));
+        for (int q = 0; q < nkept; ++q)
+            SW_HIP(hipMemcpyAsync(snap + kept[q].at, kept[q].p, kept[q].bytes, hipMemcpyDeviceToDevice, s));
         return SWARM_OK;
     }
 
     // st[0] != 0: every caller array back to its entry bytes (the unpack before it included), on the device.
     int restore_if_refused(const unsigned long long *st, hipStream_t s) const {
-        for (const Kept &k : kept) {
+        for (int q = 0; q < nkept; ++q) {
+            const Kept &k = kept[q];
             hipLaunchKernelGGL(k_restore_refused, dim3(grid_for(int64_t(k.bytes / 8 + 1), kBlock, 4096)),
                                dim3(kBlock), 0, s, st, static_cast<uint8_t *>(k.p), snap + k.at, k.bytes);
             SW_LAUNCHED();
@@ -1300,18 +1729,28 @@ int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t,
 // come back through pinned memory -- [0..3] verdict, [4] singular, [8..15] traffic, [16..] counts -- in the
 // run's one final host wait (none when nothing is asked for).  A refused tick (`snap` restores the caller's
 // arrays) withholds the counts and the singular count and sets refused_tick.
-int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap, hipStream_t s) {
+int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap,
+              const TaskState &ts, hipStream_t s) {
     const bool want_sing = r.loop && r.loop->n_singular;
+    const bool want_tasks = r.tasked() && (r.task_counts || r.n_guard);
     if (r.traffic) {  // (pull-mode runs: every tick walks every row -- the receivers are all agents)
         hipLaunchKernelGGL(k_sum_traffic, dim3(1), dim3(kWave), 0, s, c.tr_shards, c.tr_sums);
         SW_LAUNCHED();
     }
     if (ls)
         if (const int rc = snap.restore_if_refused(ls->st, s)) return rc;
-    if (!(r.traffic || ls || want_sing || r.counts)) return SWARM_OK;
+    if (!(r.traffic || ls || want_sing || r.counts || want_tasks)) return SWARM_OK;
     const size_t cnt_bytes = r.counts ? size_t(r.ticks) * 4 * 8 : 0;
-    unsigned long long *h = static_cast<unsigned long long *>(pinned(r.ctx, 128 + cnt_bytes));
+    const size_t tcnt_bytes = want_tasks ? size_t(r.ticks) * 4 * 8 : 0;  // after the counts
+    unsigned long long *h = static_cast<unsigned long long *>(pinned(r.ctx, 128 + cnt_bytes + tcnt_bytes));
     if (!h) return SWARM_ERR_OOM;
+    unsigned long long *ht = h + 16 + cnt_bytes / 8;
+    if (want_tasks) {
+        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
+                           int64_t(r.ticks), ts.part, ts.sums);
+        SW_LAUNCHED();
+        SW_HIP(hipMemcpyAsync(ht, ts.sums, tcnt_bytes, hipMemcpyDeviceToHost, s));
+    }
     if (r.traffic) SW_HIP(hipMemcpyAsync(h + 8, c.tr_sums, kTraffic * 8, hipMemcpyDeviceToHost, s));
     if (ls) SW_HIP(hipMemcpyAsync(h, ls->st, 32, hipMemcpyDeviceToHost, s));
     if (want_sing) SW_HIP(hipMemcpyAsync(h + 4, c.sing, 8, hipMemcpyDeviceToHost, s));
@@ -1331,6 +1770,14 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
     }
     if (want_sing) *r.loop->n_singular = int64_t(h[4]);
     if (r.counts) memcpy(r.counts, h + 16, cnt_bytes);
+    if (want_tasks) {
+        int64_t guard = 0;
+        for (int64_t q = 0; q < r.ticks; ++q) {
+            if (r.task_counts) for (int c = 0; c < 3; ++c) r.task_counts[3 * q + c] = int64_t(ht[4 * q + c]);
+            guard += int64_t(ht[4 * q + 3]);
+        }
+        if (r.n_guard) *r.n_guard = guard;
+    }
     return SWARM_OK;
 }
 
@@ -1339,13 +1786,15 @@ int run_ticks(const TickRun &r) {
     int rc;
     if ((rc = check_run_args(r))) return rc;
     if (r.traffic) for (int q = 0; q < kTraffic; ++q) r.traffic[q] = 0;
+    if (r.task_counts) for (int64_t q = 0; q < int64_t(r.ticks) * 3; ++q) r.task_counts[q] = 0;
+    if (r.n_guard) *r.n_guard = 0;
     if (r.n == 0 || r.ticks == 0) {
         if (r.counts) for (int64_t q = 0; q < int64_t(r.ticks) * 4; ++q) r.counts[q] = 0;
         return SWARM_OK;
     }
     hipStream_t s = static_cast<hipStream_t>(r.stream);
     const LoopArgs *loop = r.loop;
-    const bool sensed = r.sensed(), radio = r.radio(), push = r.push();
+    const bool sensed = r.sensed(), radio = r.radio(), push = r.push(), tasked = r.tasked();
     // U1-S / U1-R: the call's grid (the loop's one host wait before its end; non-finite positions are refused
     // here; U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
     LoopSense ls{};
@@ -1364,10 +1813,12 @@ int run_ticks(const TickRun &r) {
     if ((rc = pack_records(r, grid, &f, &vec, s))) return rc;
     PushState ps;
     RadioState rs;
+    TaskState ts;
     TickClocks clk;
     if (push && (rc = ps.begin(r, grid, s))) return rc;
     if ((rc = clk.begin(r, ps, s))) return rc;
-    if (radio && (rc = rs.begin(r, ls))) return rc;
+    if (radio && (rc = rs.begin(r, ls, tasked ? 3 : 1))) return rc;
+    if (tasked && (rc = ts.begin(r, s))) return rc;
     double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
     for (int64_t t = r.t0 + 1; t <= r.t0 + r.ticks; ++t) {
         // (a heartbeat sent during tick t-1 carries its sender's position of then: the loops' lagged buffer)
@@ -1381,7 +1832,8 @@ int run_ticks(const TickRun &r) {
         // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell (the call's grid reaches
         // far beyond the agents: offsets by search)
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
-        rc = radio  ? rs.launch(r, f, k, ls, s)
+        rc = tasked ? ts.launch(r, f, k, ls, rs, s)
+             : radio  ? rs.launch(r, f, k, ls, s)
              : push ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
                     : launch_tick_pull(r, grid, f, k, s);
         if (rc) return rc;
@@ -1396,7 +1848,7 @@ int run_ticks(const TickRun &r) {
     hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, r.fsm->state, r.fsm->alive,
                        r.fsm->has_leader_pos, r.fsm->leader, reinterpret_cast<float2 *>(r.fsm->leader_pos), f);
     SW_LAUNCHED();
-    return read_back(r, cnt, sensed ? &ls : nullptr, snap, s);
+    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts, s);
 }
 
 // The three loop entry points' own arguments (run_ticks checks the rest): U1 takes a sensor CSR and n < 2^31,
@@ -1422,6 +1874,30 @@ int check_loop_args(LoopKind kind, swarm_ctx *ctx, int64_t n, int32_t ticks, dou
         SW_ARG((p > q ? p - q : q - p) >= uintptr_t(n) * 16, "pos and pos_prev must not overlap");
         SW_ARG((p & 15) == 0 && (q & 15) == 0, "pos / pos_prev are not 16-byte aligned");
     }
+    return SWARM_OK;
+}
+
+// swarm_update_loop_tasks' own argument: the board and the task arrays (T == 0: none is looked at).  The
+// required capabilities are read back from the device (T <= 64 bytes, one host wait) so that a bad one is
+// refused before anything is written.
+int check_tasks(swarm_ctx *ctx, int64_t n, const swarm_tasks *b, void *stream) {
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(b != nullptr, "tasks is NULL");
+    SW_ARG(b->T >= 0 && b->T <= kMaxTasks, "T must be in [0, 64]");
+    if (b->T == 0) return SWARM_OK;
+    SW_ARG(b->tpos && b->treq, "NULL task array");
+    SW_ARG(n <= 0 || (b->caps && b->status_lo && b->status_hi && b->claim_out && b->conflict_out && b->tab_winner &&
+                      b->tab_util),
+           "NULL task array");
+    auto al = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    SW_ARG(al(b->tpos, 16), "tpos is not 16-byte aligned");
+    SW_ARG(n <= 0 || (al(b->status_lo, 8) && al(b->status_hi, 8) && al(b->claim_out, 8) && al(b->conflict_out, 8)),
+           "a task word array is not 8-byte aligned");
+    int8_t rq[kMaxTasks];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SW_HIP(hipMemcpyAsync(rq, b->treq, size_t(b->T), hipMemcpyDeviceToHost, s));
+    SW_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < b->T; ++k) SW_ARG(!bad_req(rq[k]), "a treq outside [-1, 31]");
     return SWARM_OK;
 }
 
@@ -1499,6 +1975,26 @@ int swarm_update_loop_radio(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                         trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
     return run_loop(kLoopRadio, {ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
                                  timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream});
+}
+
+int swarm_update_loop_tasks(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                            const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                            double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                            int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                            const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                            double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                            int64_t *refused_tick, const swarm_tasks *tasks, int64_t *task_counts,
+                            int64_t *n_guard, void *stream) {
+    using namespace swarm;
+    if (const int rc = check_tasks(ctx, n, tasks, stream)) return rc;
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
+                        trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
+    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream};
+    r.tasks = tasks;
+    r.task_counts = task_counts;
+    r.n_guard = n_guard;
+    return run_loop(kLoopRadio, r);
 }
 
 }  // extern "C"

@@ -64,6 +64,8 @@ enum Slot {
     S_LOOP_SNAP,      // sensed update loop: the caller's arrays as they were at entry (restored on a refusal)
     S_RADIO_OUTBOX,   // radio update loop: the tick's inbound outbox bytes in cell-sorted order
     S_RADIO_CELLS,    // radio update loop: one byte per grid cell, set when the cell holds a sender
+    S_TASK_COUNTS,    // task update loop: the per-tick task counters (sharded) and their sums
+    S_TASK_SENDERS,   // task update loop: one byte per agent and tick parity, what it sent (outbox + task bits)
     S_NUM
 };
 

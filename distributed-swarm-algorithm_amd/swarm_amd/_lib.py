@@ -38,7 +38,7 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_comm_unique_id_kind", "swarm_comm_create_kind", "swarm_comm_kind", "swarm_allocate_indexed_ex",
            "swarm_protocol_run_ex", "swarm_elect_sharded_ex", "swarm_graph_compact_escaped",
            "swarm_frontier_set_compact_escaped", "swarm_physics_run_sensed", "swarm_update_loop",
-           "swarm_update_loop_sensed", "swarm_update_loop_radio")
+           "swarm_update_loop_sensed", "swarm_update_loop_radio", "swarm_update_loop_tasks")
 
 
 class SwarmError(RuntimeError):
@@ -50,6 +50,13 @@ class SwarmError(RuntimeError):
 class Fsm(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("state", "leader", "last_hb", "wait_start", "delay", "leader_pos",
                                                "has_leader_pos", "alive", "outbox")]
+
+
+class Tasks(ctypes.Structure):
+    """swarm_tasks: the board and every agent's task state (device pointers)."""
+    _fields_ = [("T", ctypes.c_int32)] + \
+               [(k, ctypes.c_void_p) for k in ("tpos", "treq", "caps", "status_lo", "status_hi", "claim_out",
+                                               "conflict_out", "tab_winner", "tab_util")]
 
 
 class AllocStats(ctypes.Structure):
@@ -176,6 +183,8 @@ def load(path: str = LIB_PATH):
         L.swarm_update_loop_radio.argtypes = [P, i64, P, P, P, P, ctypes.POINTER(Fsm), i64, i32, d, d, d,
                                               ctypes.c_uint64, P, i32, P, P, P, i64, P, d, d, d, P, i32, P,
                                               ctypes.POINTER(i64), ctypes.POINTER(i64), P]
+        L.swarm_update_loop_tasks.argtypes = L.swarm_update_loop_radio.argtypes[:-1] + [
+            ctypes.POINTER(Tasks), P, ctypes.POINTER(i64), P]
         L.swarm_auction_begin.argtypes = [P, i64, P, P, P, i64, P, P, d, d, ctypes.c_float, P, P, P, P, P]
         L.swarm_auction_bid.argtypes = [P, i64, i32, i32, P, P, P, P]
         L.swarm_auction_resolve.argtypes = [P, i64, i32, P, P, P, P, P, P]

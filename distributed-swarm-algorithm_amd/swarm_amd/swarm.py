@@ -799,10 +799,90 @@ class Swarm:
         return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
                                  max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius)
 
+    # ------------------------------------------------------------------ task update loop (U1-T)
+    def set_tasks(self, tx, ty=None, treq=None):
+        """A fresh task board shared by every agent (each reference agent's `tasks` dict holding all T tasks,
+        T <= 64): every task OPEN at every agent, every claim table empty, no claim or conflict in flight.
+        tx / ty: task positions; treq: required capability bit per task, -1 = none (default).  A
+        tasks_from_dict result (task_ids, tx, ty, treq) may be given as the only argument; its task_ids are
+        kept in self.task_ids.  update_loop_tasks then runs the board; T and treq are checked there, by the
+        library (SwarmError ERR_ARG, nothing written)."""
+        ids = None
+        if ty is None and isinstance(tx, tuple) and len(tx) == 4:
+            ids, tx, ty, treq = tx
+        tx = np.atleast_1d(np.asarray(tx, np.float64))
+        ty = np.atleast_1d(np.asarray(ty, np.float64))
+        if tx.ndim != 1 or tx.shape != ty.shape:
+            raise ValueError("tx and ty must be 1-D arrays of one length")
+        T, n, dev = int(tx.shape[0]), self.n, self.device
+        tq = np.full(T, -1, np.int8) if treq is None else np.atleast_1d(np.asarray(treq)).astype(np.int64)
+        if tq.shape != (T,):
+            raise ValueError(f"treq: expected {T} values, got shape {tuple(tq.shape)}")
+        if T and (int(tq.min()) < -128 or int(tq.max()) > 127):
+            raise ValueError("treq must fit a signed byte (the library accepts -1 .. 31)")
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)  # noqa: E731  (u64 words)
+        self.tasks = dict(T=T, tpos=torch.as_tensor(np.stack([tx, ty], 1), device=dev).contiguous(),
+                          treq=torch.as_tensor(tq.astype(np.int8), device=dev), status_lo=z(n), status_hi=z(n),
+                          claim_out=z(2 * n), conflict_out=z(2 * n),
+                          tab_winner=torch.full((n, T), -1, dtype=torch.int32, device=dev),
+                          tab_util=torch.zeros((n, T), dtype=torch.float32, device=dev))
+        self.task_ids = np.arange(T, dtype=np.int64) if ids is None else np.asarray(ids, np.int64)
+        return self
+
+    def update_loop_tasks(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
+                          kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
+                          max_speed: float = 5.0, trace_every: int = 0) -> dict:
+        """update_loop_radio with the reference's task logic run every tick on the board of set_tasks
+        (contract U1-T; swarm_update_loop_tasks; agent.py:292-336): an agent claims a task on the tick it is
+        within reach of it (U > 20 at the tick's snapshot) and marks it TENTATIVE; only a LEADER that hears
+        the claim arbitrates, in its own claim table, with the 5.0 hysteresis; its TASK_CONFLICT messages set
+        the task ASSIGNED at the winner and LOCKED at everyone else who hears them, the last one heard (in
+        ascending storage index) deciding; a claim no leader hears is lost.  Keywords, self.fsm /
+        self.fsm_tick / self.pos_prev, the all-or-nothing refusal (every task array restored as well) and the
+        chaining with the other three loops as update_loop_radio; claims and conflicts in flight carry over
+        between calls.  Returns update_loop_radio's dict plus "task_counts" (ticks x 3: TASK_CLAIMs sent,
+        claims handled by a LEADER, TASK_CONFLICT messages sent) and "guard", the evaluated (agent, task)
+        pairs whose utility is so close to 20 that libm pow arithmetic could have decided differently."""
+        if not hasattr(self, "tasks"):
+            raise RuntimeError("no task board: call set_tasks() first")
+        radio_radius, sense_radius = float(radio_radius), float(sense_radius)
+        for name, r in (("radio_radius", radio_radius), ("sense_radius", sense_radius)):
+            if not (r > 0.0 and np.isfinite(r)):
+                raise ValueError(f"{name} must be positive and finite, got {r}")
+        return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
+                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius, tasks=self.tasks)
+
+    def task_status(self) -> torch.Tensor:
+        """(n, T) uint8 status codes (indices into STATUS_NAMES), storage order."""
+        b = self.tasks
+        k = torch.arange(b["T"], dtype=torch.int64, device=self.device)[None, :]
+        lo, hi = (b["status_lo"][:, None] >> k) & 1, (b["status_hi"][:, None] >> k) & 1
+        return (lo | (hi << 1)).to(torch.uint8)
+
+    def task_tables(self):
+        """Every agent's task_claims as dense tables, storage order: (winner (n, T) int32, -1 = no entry;
+        utility (n, T) float32)."""
+        return self.tasks["tab_winner"], self.tasks["tab_util"]
+
+    def write_back_tasks(self, agents, task_ids=None):
+        """Status strings into every agent object's `tasks` dict and its task_claims (agent.py:41-44), as the
+        loop left them; agents in input order, task_ids[k]: the dict key of board task k (default:
+        self.task_ids)."""
+        task_ids = self.task_ids if task_ids is None else task_ids
+        st = self.to_input_order(self.task_status())
+        w, u = (self.to_input_order(t) for t in self.task_tables())
+        for i, a in enumerate(agents):
+            for k, tid in enumerate(task_ids):
+                task = a.tasks.get(int(tid))
+                if task is not None:
+                    task["status"] = STATUS_NAMES[st[i, k]]
+            a.task_claims = {int(tid): {"winner": int(w[i, k]), "utility": float(u[i, k])}
+                             for k, tid in enumerate(task_ids) if w[i, k] >= 0}
+
     def _update_loop(self, ticks, sense_radius, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed,
-                     max_speed, mode, pull_frac, trace_every, radio_radius=None) -> dict:
-        """update_loop (sense_radius None: the `sensors` lists, fixed), update_loop_sensed and
-        update_loop_radio (radio_radius given: no message graph)."""
+                     max_speed, mode, pull_frac, trace_every, radio_radius=None, tasks=None) -> dict:
+        """update_loop (sense_radius None: the `sensors` lists, fixed), update_loop_sensed,
+        update_loop_radio (radio_radius given: no message graph) and update_loop_tasks (tasks: the board)."""
         ticks, trace_every = int(ticks), int(trace_every)
         if mode not in ("push", "pull", "hybrid"):
             raise ValueError(f"unknown mode {mode!r}")
@@ -852,7 +932,22 @@ class Swarm:
                     *(() if radio_radius is not None else (float(pull_frac) if mode == "hybrid" else -1.0,)), *motion)
             tail = (float(max_speed), _lib.ptr(trace) if frames and n else None, trace_every,
                     counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(sing))
-            if radio_radius is not None:
+            if tasks is not None:
+                T = tasks["T"]
+                if any(tasks[k].shape[0] != size for k, size in (("status_lo", n), ("claim_out", 2 * n))):
+                    raise ValueError("the task board was set for another number of agents")
+                tp = lambda k: _lib.ptr(tasks[k]) if tasks[k].numel() else None  # noqa: E731
+                tk = _lib.Tasks(T, tp("tpos"), tp("treq"), p(self.caps) if T else None,
+                                *[tp(k) for k in ("status_lo", "status_hi", "claim_out", "conflict_out",
+                                                  "tab_winner", "tab_util")])
+                task_counts = np.zeros((ticks, 3), np.int64)
+                guard = ctypes.c_int64(0)
+                rc = _lib.lib().swarm_update_loop_tasks(*head, float(radio_radius), float(sense_radius), *tail,
+                                                        ctypes.byref(refused), ctypes.byref(tk),
+                                                        task_counts.ctypes.data_as(ctypes.c_void_p),
+                                                        ctypes.byref(guard), _lib.stream())
+                self.last_refused_tick = refused.value
+            elif radio_radius is not None:
                 rc = _lib.lib().swarm_update_loop_radio(*head, float(radio_radius), float(sense_radius), *tail,
                                                         ctypes.byref(refused), _lib.stream())
                 self.last_refused_tick = refused.value
@@ -872,6 +967,8 @@ class Swarm:
         out = {"counts": counts, "singular": sing.value}
         if trace_every:
             out["trace"] = trace
+        if tasks is not None:
+            out["task_counts"], out["guard"] = task_counts, guard.value
         return out
 
     # ------------------------------------------------------------------ views / bridge

@@ -685,6 +685,67 @@ int swarm_update_loop_radio(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
                             int64_t *refused_tick, void *stream);
 
+/*
+ * swarm_update_loop_radio with _process_logic's third step, _process_tasks, and the two task handlers
+ * (agent.py:292-336) run every tick (contract U1-T).  A board of T <= 64 tasks is shared by all
+ * agents (every agent's `tasks` dict holds all T).  Tick t, with U1-R's snapshot and walk:
+ *   receive   alive agent i walks its heard senders j in ascending storage index; for each j it handles j's
+ *             packets of tick t-1 as swarm_update_loop_radio does and then j's TASK_CLAIMs, which count only
+ *             if i is LEADER at that moment (after j's election packets, before sender j+1's).  A claim on
+ *             task k with utility u (f32; computed from the position its sender claimed at, P_{t-2}) takes
+ *             i's table entry when that is empty or u > held + 5.0 (the f32 values widened to fp64) and sends a
+ *             TASK_CONFLICT naming the claimer; otherwise, when the held winner is another agent, it sends one
+ *             naming the held winner.  j's TASK_CONFLICTs set i's status of the task to ASSIGNED when the
+ *             winner is i's ID, else LOCKED, whatever i's state and whoever j is; the last conflict on a task
+ *             in walk order wins.
+ *   logic     after the timers and the heartbeat, every task still OPEN with U(P_{t-1}[i], caps[i], task) >
+ *             20.0 (fp64, swarm_allocate's arithmetic) becomes TENTATIVE and is claimed.  No status returns to
+ *             OPEN.  Dead agents neither claim, arbitrate nor change status; what they sent before dying still
+ *             arrives.  A table survives its owner losing leadership.
+ * swarm_tasks, everything on the device, the per-agent arrays in/out so that a run split into chunks is the
+ * same run with claims and conflicts in flight across the boundary:
+ *   T, tpos (T x 2 f64), treq (T i8: -1 none, else a capability bit 0..31), caps (n u32): as swarm_allocate;
+ *   status_lo / status_hi (n u64 each): bit k of the two words is task k's 2-bit status -- 0 OPEN,
+ *             1 TENTATIVE, 2 LOCKED, 3 ASSIGNED;
+ *   claim_out / conflict_out (2n u64 each, by tick parity as the outbox): bit k of word (t & 1) n + i -- agent
+ *             i claimed task k during tick t / sent at least one TASK_CONFLICT on it (the message names the
+ *             winner its table held at the end of that tick's receive);
+ *   tab_winner (n x T i32, -1 empty) / tab_util (n x T f32): every agent's task_claims.
+ * The dense table costs 8 T bytes per agent, and the ctx keeps the same again (plus 48 bytes per agent for the
+ * other task words) in the entry snapshot, and 2 bytes per agent of scratch; a sparse table and T > 64 are
+ * out of scope.
+ * task_counts (host, ticks x 3, may be NULL): per tick, TASK_CLAIMs sent, claims handled by a LEADER,
+ * TASK_CONFLICT messages sent.  n_guard (host, may be NULL): evaluated (agent, OPEN task) pairs of the run whose
+ * utility lies where libm pow arithmetic for the squares could have decided differently (swarm_allocate's
+ * guard band around 20.0); the loop has no host wait, so nothing is deferred -- the caller learns whether
+ * the run may differ from the reference's.
+ * SWARM_ERR_ARG (nothing written): tasks NULL, T outside [0, 64], a treq outside [-1, 31] (read back from the
+ * device before anything is launched), a NULL array with T > 0, and whatever swarm_update_loop_radio refuses.
+ * The all-or-nothing refusal of a too-dense tick restores every task array as well and withholds task_counts
+ * and n_guard.  T == 0: swarm_update_loop_radio, task_counts zeroed, *n_guard = 0, no task array touched.
+ */
+typedef struct {
+    int32_t T;
+    const double *tpos;
+    const int8_t *treq;
+    const uint32_t *caps;
+    uint64_t *status_lo;
+    uint64_t *status_hi;
+    uint64_t *claim_out;
+    uint64_t *conflict_out;
+    int32_t *tab_winner;
+    float *tab_util;
+} swarm_tasks;
+
+int swarm_update_loop_tasks(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                            const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                            double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                            int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                            const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                            double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                            int64_t *refused_tick, const swarm_tasks *tasks, int64_t *task_counts,
+                            int64_t *n_guard, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
