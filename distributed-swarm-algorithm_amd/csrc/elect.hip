@@ -658,13 +658,57 @@ __device__ __forceinline__ unsigned take_stamps(int64_t v0, int64_t n, W wv, uns
     return mask;
 }
 
+// The cheaper form of the same test (LF_FAST).  Bit 7 of every byte of the result: that byte of w
+// differs from the stamp byte replicated in b4 (the other bits are not used).
+__device__ __forceinline__ unsigned bytes_ne(unsigned w, unsigned b4) {
+    const unsigned x = w ^ b4;
+    return ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x;
+}
+__device__ __forceinline__ unsigned stamp_word(uint2 w, int i) { return i ? w.y : w.x; }
+__device__ __forceinline__ unsigned stamp_word(uint16_t w, int) { return w; }  // high bytes 0: never a stamp
+
+// k_sparse_block's flags argument
+constexpr unsigned SF_CLEAR = 1u;        // zero every stamp word after loading it (the next round's 256-round clear)
+constexpr unsigned SF_GUARD_EARLY = 2u;  // SWARM_GUARD_LATE=0: the guard word read and waited for before the stamps
+// The list-phase levers of k_sparse_block ("list phase"): a template argument, not flag bits --
+// with both forms of each part in one kernel the former code alone ran 4 % slower at 10M agents (scalar
+// registers spilled into the gather loop; DESIGN_LOG.md r15).  0 is the former code.
+constexpr unsigned LF_FAST = 1u;         // SWARM_LIST_FAST: marked lanes from one shift per stamp word (fast_masks)
+constexpr unsigned LF_VOTE = 2u;         // SWARM_LIST_VOTE: a wave none of whose lanes is marked skips scan and list
+constexpr unsigned LF_ATOMIC = 4u;       // SWARM_LIST_ATOMIC: waves reserve list slices with one LDS add; one barrier
+constexpr unsigned LF_FLUSH_VOTE = 8u;   // SWARM_FLUSH_VOTE: a wave that gathered nothing skips its counter sums
+constexpr unsigned LF_FLUSH_WAVE = 16u;  // SWARM_FLUSH_WAVE: counters added per wave, no LDS reduction or barrier
+constexpr unsigned kListAll = 31u;
+constexpr unsigned kListDefault = LF_VOTE | LF_ATOMIC;  // by the A/B rule (DESIGN_LOG.md r15)
+#ifndef SWARM_LIST_EXTRA  // one more combination for an A/B build (tools/build_variant.sh NAME "-DSWARM_LIST_EXTRA=5")
+#define SWARM_LIST_EXTRA 0
+#endif
+constexpr bool list_mask_compiled(unsigned m) {
+    return m == 0u || m == kListAll || m == kListDefault || m == unsigned(SWARM_LIST_EXTRA);
+}
+
 // my_act / my_edges: this lane's marked agents and edges of the round (32-bit per lane: VGPRs are
 // at the 8-waves-per-SIMD cap in the sparse kernel)
+template <unsigned LF>
 __device__ __forceinline__ void flush_counts(unsigned long long *ring, int t, long long my_chg, int my_act,
                                              int my_edges, long long (*s_red)[kWavesPerBlock]) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    my_act = wave_sum(my_act);
-    my_edges = wave_sum(my_edges);
+    // a wave that gathered no agent (most waves of a tail round) has three zeros to add: one vote instead of
+    // two wave sums (my_chg counts risers among the gathered agents: 0 as well)
+    const bool quiet = (LF & LF_FLUSH_VOTE) && __ballot(my_act != 0) == 0ull;
+    if (quiet) {
+        my_act = my_edges = 0;
+    } else {
+        my_act = wave_sum(my_act);
+        my_edges = wave_sum(my_edges);
+    }
+    if (LF & LF_FLUSH_WAVE) {  // each wave adds its own sums to the workgroup's shard, fire and forget
+        if (!quiet && lane < 3) {
+            const long long a = lane == 0 ? my_chg : lane == 1 ? (long long)my_act : (long long)my_edges;
+            if (a) atomicAdd(slot(ring, t, lane, blockIdx.x & (kShards - 1)), (unsigned long long)a);
+        }
+        return;
+    }
     if (lane == 0) {
         s_red[0][wid] = my_chg;  // wave-uniform (ballot counts)
         s_red[1][wid] = my_act;
@@ -693,10 +737,6 @@ struct SparseRest {
     const int32_t *hcol;
 };
 
-// k_sparse_block's flags argument
-constexpr unsigned SF_CLEAR = 1u;        // zero every stamp word after loading it (the next round's 256-round clear)
-constexpr unsigned SF_GUARD_EARLY = 2u;  // SWARM_GUARD_LATE=0: the guard word read and waited for before the stamps
-
 // A wave-uniform 8-byte word no thread of this kernel writes, read with a scalar load (the scalar cache
 // is invalidated at kernel start, so a word the previous kernel wrote is read from L2 or beyond).
 __device__ __forceinline__ unsigned long long scalar_ld8(const unsigned long long *p) {
@@ -710,7 +750,7 @@ __device__ __forceinline__ unsigned long long scalar_ld8(const unsigned long lon
 // stamp words round t reads; nchunks and ng (the grid size).  guard_word: &tot[(t - 2) % kRing] or
 // NULL (guard off); stamp4: round t's stamp byte in all four bytes.
 template <typename Off, int S = kScan, bool DIR = false, typename CT = Col32, int G = kG, int K = kKs,
-          bool PRUNE = false>
+          bool PRUNE = false, unsigned LF = 0>
 __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_block(
     uint8_t *__restrict__ ar, const unsigned long long *guard_word, const int32_t *__restrict__ P,
     const Off *__restrict__ rp, uint32_t nchunks, uint32_t ng, int t, unsigned stamp4, unsigned flags,
@@ -719,6 +759,7 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
     constexpr int kChunk = kBlock * S;
     __shared__ int s_list[kListCap];
     __shared__ int s_wave[kWavesPerBlock];
+    __shared__ int s_cnt[2];  // LF_ATOMIC: list entries reserved so far, by passes of even / odd number
     __shared__ long long s_red[3][kWavesPerBlock];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #ifdef SWARM_PHASES  // debug build: per-workgroup start/end clocks, marked agents (sum, max chunk)
@@ -770,6 +811,12 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
     load_group(blockIdx.x);
     if (guard_word && !(flags & SF_GUARD_EARLY)) prev2 = scalar_ld8(guard_word);
     __builtin_amdgcn_sched_barrier(0);  // nothing that waits for a struct field moves in front of the loads
+    // LF_ATOMIC: the list counters start at 0.  Their barrier comes here, under the stamp loads' flight:
+    // written as instructions, because __syncthreads() would wait for the loads too (its fence is vmcnt(0)).
+    if (LF & LF_ATOMIC) {
+        if (threadIdx.x == 0) s_cnt[0] = s_cnt[1] = 0;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
     int32_t *__restrict__ Q = a.Q;
     uint8_t *aw = a.aw;
     const CT cols = a.cols;
@@ -793,40 +840,121 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
         }
         return masks;
     };
+    // LF_FAST: the same marked lanes for a third of the instructions.  Word k of the group (k = p * kWords
+    // + i: word i of preloaded chunk p) has one "byte differs" bit per stamp (bytes_ne); one shift moves them
+    // to bit k of each byte, so mask bit 8 * b + k is stamp 4 * i + b of chunk p (list_agent decodes it) and no
+    // bits are gathered per chunk.  A chunk that is absent drops out by a scalar mask.  The past-the-end
+    // test runs only for a chunk that can reach n_rows -- its last block position's block ends past it: the
+    // last real chunk in agent order, the last C / B chunks in the interleaved layout, a scalar test -- and
+    // in 32 bits in the int32 instantiation (n_rows < 2^30, checked by the host).
+    constexpr int kWords = S == 8 ? 2 : 1;
+    using NV = std::conditional_t<sizeof(Off) == 4, uint32_t, uint64_t>;
+    auto fast_masks = [&](uint32_t cg) {
+        unsigned ne = 0, live = 0;
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            if (cg + p * NG < nchunks) live |= (kWords == 2 ? 0x03030303u : 0x01010101u) << (p * kWords);
+#pragma unroll
+            for (int i = 0; i < kWords; ++i) {
+                const int k = p * kWords + i;
+                ne |= (bytes_ne(stamp_word(wv[p], i), stamp4) >> (7 - k)) & (0x01010101u << k);
+            }
+        }
+        unsigned m = ~ne & live;
+        const uint32_t posmax = (1u << (a.sm.cshift - a.sm.bshift)) - 1u;  // a chunk's last block position
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const uint32_t chunk = cg + p * NG;
+            if (chunk < nchunks && (NV(posmax * a.sm.M + chunk + 1u) << a.sm.bshift) > NV(n)) {
+                const NV v0 = NV(uint32_t(stamp_agent(a.sm, chunk, j0)));
+#pragma unroll
+                for (int o = 0; o < S; ++o)
+                    if (v0 + NV(o) >= NV(n)) m &= ~(1u << (8 * (o & 3) + p * kWords + (o >> 2)));
+            }
+        }
+        return m;
+    };
+    // The agent of a mask bit.  stamp_agent is linear in the chunk number (the chunk is added to the block
+    // number in front of the shift, and the low bshift bits are the thread's own): chunk cg + p * NG is
+    // p * (NG << bshift) agents behind chunk cg, a scalar product.
+    auto list_agent = [&](uint32_t cg, int bit) {
+        if (LF & LF_FAST) {
+            const int k = bit & 7;
+            return int(uint32_t(stamp_agent(a.sm, cg, j0)) + uint32_t(k / kWords) * (NG << a.sm.bshift)) +
+                   (k % kWords) * 4 + (bit >> 3);
+        }
+        return int(stamp_agent(a.sm, cg + (bit >> kLogS) * NG, j0)) + (bit & (S - 1));
+    };
     uint32_t cg = blockIdx.x;
     bool more = prev2 != 0;  // converged: nothing is marked
-    unsigned masks = more ? group_masks(cg) : 0u;
+    unsigned masks = !more ? 0u : (LF & LF_FAST) ? fast_masks(cg) : group_masks(cg);
 #ifdef SWARM_PHASES
     ph_stamps = wall_clock64() + (masks & 0);
 #endif
+    // LF_ATOMIC: s_cnt[ci] is the counter of this pass of the loop below, seen_cur what it held when the
+    // pass began.  The counters only grow (a round lists each agent once: < 2^31) and alternate, so there is
+    // nothing to reset between passes: a pass's total is read between its barrier and the next pass's, and
+    // the same counter is added to again only behind that next barrier.
+    int ci = 0, seen_cur = 0, seen_oth = 0;
     while (more) {
         // append the group's marked agents, gathering whenever the list fills up
         for (;;) {
-            const int cnt = __popc(masks);  // <= kPre * S <= 32
-            int wtot;
-            const int excl = wave_excl_scan<6>(cnt, wtot);
-            if (lane == 0) s_wave[wid] = wtot;
-            __syncthreads();
-            int off = 0, total = 0;
+            // LF_VOTE: a wave with no marked lane (most waves of a tail round, whose front is a run of
+            // consecutive agents) contributes 0 and goes straight to the barrier(s) every wave arrives at
+            const bool some = !(LF & LF_VOTE) || __ballot(masks != 0) != 0ull;  // wave-uniform
+            int total;
+            if (LF & LF_ATOMIC) {
+                // Each wave reserves its slice [base, base + wtot) of the list with one LDS add by one lane:
+                // one barrier per pass, where the s_wave exchange needs two more.  The order of the slices is
+                // whatever order the adds arrive in.  Nothing a caller sees depends on it: a round's listed
+                // agents are independent (each reads leaders of round t-1 and writes its own entry), the marks
+                // they leave are byte stores of one value, and the counters are sums.
+                if (some) {
+                    int wtot;
+                    const int excl = wave_excl_scan<6>(__popc(masks), wtot);
+                    int base = 0;
+                    if (lane == 0 && wtot) base = atomicAdd(&s_cnt[ci], wtot);
+                    int pos = listed + (__builtin_amdgcn_readfirstlane(base) - seen_cur) + excl;
+                    while (masks && pos < kListCap) {  // entries past the cap stay in masks for the next pass
+                        const int bit = __ffs(masks) - 1;
+                        masks &= masks - 1;
+                        s_list[pos++] = list_agent(cg, bit);
+                    }
+                }
+                __syncthreads();  // every wave's add and list entries
+                const int now = __builtin_amdgcn_readfirstlane(s_cnt[ci]);
+                total = now - seen_cur;
+                seen_cur = seen_oth;
+                seen_oth = now;
+                ci ^= 1;
+                if (total == 0) break;
+            } else {
+                int excl = 0, wtot = 0;
+                if (some) excl = wave_excl_scan<6>(__popc(masks), wtot);  // counts <= kPre * S <= 32
+                if (lane == 0) s_wave[wid] = wtot;
+                __syncthreads();
+                int off = 0;
+                total = 0;
 #pragma unroll
-            for (int w = 0; w < kWavesPerBlock; ++w) {
-                off += (w < wid) ? s_wave[w] : 0;
-                total += s_wave[w];
+                for (int w = 0; w < kWavesPerBlock; ++w) {
+                    off += (w < wid) ? s_wave[w] : 0;
+                    total += s_wave[w];
+                }
+                __syncthreads();  // s_wave read by all
+                if (total == 0) break;
+                int pos = listed + off + excl;
+                while (masks && pos < kListCap) {
+                    const int bit = __ffs(masks) - 1;
+                    masks &= masks - 1;
+                    s_list[pos++] = list_agent(cg, bit);
+                }
+                __syncthreads();  // list entries visible
             }
-            __syncthreads();  // s_wave read by all
-            if (total == 0) break;
 #ifdef SWARM_PHASES
             ph_sum += total;
             ph_max = total > ph_max ? total : ph_max;
 #endif
-            int pos = listed + off + excl;
-            while (masks && pos < kListCap) {
-                const int bit = __ffs(masks) - 1;
-                masks &= masks - 1;
-                s_list[pos++] = int(stamp_agent(a.sm, cg + (bit >> kLogS) * NG, j0)) + (bit & (S - 1));
-            }
             listed = listed + total < kListCap ? listed + total : kListCap;
-            __syncthreads();  // list entries visible
             if (listed < kListCap) break;  // everything fitted
             gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
                                           kBlock / G, a.c_lo, a.n_count, my_chg, my_act, my_edges);
@@ -837,7 +965,7 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
         more = cg < nchunks;
         if (more) {
             load_group(cg);
-            masks = group_masks(cg);
+            masks = (LF & LF_FAST) ? fast_masks(cg) : group_masks(cg);
         }
     }
 #ifdef SWARM_PHASES
@@ -851,7 +979,7 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
 #endif
     // (behind the workgroup's own round: in front of it the stamp words it holds in flight were spilled)
     bookkeeping_last(a.ring, a.tot, t, ng);
-    flush_counts(a.ring, t, my_chg, my_act, my_edges, s_red);
+    flush_counts<LF>(a.ring, t, my_chg, my_act, my_edges, s_red);
 #ifdef SWARM_PHASES
     if (threadIdx.x == 0 && blockIdx.x < 8192) {
         g_phase[blockIdx.x * 8 + 0] = ph_t0;
@@ -1299,7 +1427,22 @@ struct Tuning {
                                // are dense (round 1 reads ids; the two rounds write every entry of both buffers)
     int fused_readback = 0;    // SWARM_FUSED_READBACK: a batch's totals and its epoch word from one launch by one
                                // workgroup (0: k_batch_totals over one wave per round, then k_signal)
+    // The list phase of a sparse round ("list phase"; DESIGN_LOG.md, r15), each 0 = the former code;
+    // on by default as in kListDefault.  The kernel takes them as a template argument: the combinations
+    // compiled are none, all, the default and -DSWARM_LIST_EXTRA=mask (list_mask_compiled), any other is an error.
+    int list_fast;             // SWARM_LIST_FAST: marked lanes from one shift per stamp word, the chunk's agents by
+                               // a scalar step, the past-the-end test only where a chunk can reach n_rows
+    int list_vote;             // SWARM_LIST_VOTE: a wave with no marked lane skips the scan and the list
+    int list_atomic;           // SWARM_LIST_ATOMIC: list slices reserved by one LDS add per wave, one barrier
+    int flush_vote;            // SWARM_FLUSH_VOTE: a wave that gathered nothing skips its counter sums
+    int flush_wave;            // SWARM_FLUSH_WAVE: per-wave counter adds in place of the LDS reduction
+    unsigned list_mask = 0;    // the LF_ bits of the five above
     Tuning() {
+        list_fast = env_int("SWARM_LIST_FAST", (kListDefault & LF_FAST) != 0);
+        list_vote = env_int("SWARM_LIST_VOTE", (kListDefault & LF_VOTE) != 0);
+        list_atomic = env_int("SWARM_LIST_ATOMIC", (kListDefault & LF_ATOMIC) != 0);
+        flush_vote = env_int("SWARM_FLUSH_VOTE", (kListDefault & LF_FLUSH_VOTE) != 0);
+        flush_wave = env_int("SWARM_FLUSH_WAVE", (kListDefault & LF_FLUSH_WAVE) != 0);
         guard_late = env_int("SWARM_GUARD_LATE", 1);
         clear_inline = env_int("SWARM_CLEAR_INLINE", 0);
         skip_init_copy = env_int("SWARM_SKIP_INIT_COPY", 0);
@@ -1323,6 +1466,8 @@ struct Tuning {
         if (dense_blocks < 1) dense_blocks = 1;
         if (dense_rounds < 0) dense_rounds = 0;
         if (sparse_blocks < 1) sparse_blocks = 1;
+        list_mask = (list_fast ? LF_FAST : 0u) | (list_vote ? LF_VOTE : 0u) | (list_atomic ? LF_ATOMIC : 0u) |
+                    (flush_vote ? LF_FLUSH_VOTE : 0u) | (flush_wave ? LF_FLUSH_WAVE : 0u);
     }
 };
 
@@ -1462,17 +1607,32 @@ RoundKind plan_round(int t) {
 }
 
 // One k_sparse_block launch: the leading arguments resolved here from the frontier and the round.
-template <typename Off, int S, bool DIR, typename CT, bool PRUNE>
-void launch_sparse(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
-                   const int32_t *hcol, hipStream_t s) {
+template <typename Off, int S, bool DIR, typename CT, bool PRUNE, unsigned LF>
+void launch_sparse_lf(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
+                      const int32_t *hcol, hipStream_t s) {
     const unsigned grid = grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks));
     const SparseRest<Off, CT> a{f.L[t & 1], f.act[(t + 1) & 1], f.ring, f.tot, f.n_rows, f.c_lo, f.n_count,
                                 f.sm,       f.wsm,              cols,   hrp,   hcol};
     const unsigned long long *gw = (guard && t > 2) ? f.tot + (t - 2) % kRing : nullptr;
     if (!tuning().guard_late) flags |= SF_GUARD_EARLY;
-    hipLaunchKernelGGL((k_sparse_block<Off, S, DIR, CT, kG, kKs, PRUNE>), dim3(grid), dim3(kBlock), 0, s, f.act[t & 1],
-                       gw, static_cast<const int32_t *>(f.L[(t - 1) & 1]), rp, uint32_t(f.sm.M), uint32_t(grid), t,
-                       unsigned(stamp_of(t)) * 0x01010101u, flags, a);
+    hipLaunchKernelGGL((k_sparse_block<Off, S, DIR, CT, kG, kKs, PRUNE, LF>), dim3(grid), dim3(kBlock), 0, s,
+                       f.act[t & 1], gw, static_cast<const int32_t *>(f.L[(t - 1) & 1]), rp, uint32_t(f.sm.M),
+                       uint32_t(grid), t, unsigned(stamp_of(t)) * 0x01010101u, flags, a);
+}
+
+// The kernel of the process's list-phase levers (launch_frontier_round has checked that it is compiled).
+template <typename Off, int S, bool DIR, typename CT, bool PRUNE>
+void launch_sparse(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
+                   const int32_t *hcol, hipStream_t s) {
+    const unsigned m = tuning().list_mask;
+    if (m == kListDefault)
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, kListDefault>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+    else if (m == 0u)
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, 0u>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+    else if (m == kListAll)
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, kListAll>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+    else
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, unsigned(SWARM_LIST_EXTRA)>(rp, cols, f, t, guard, flags, hrp, hcol, s);
 }
 
 // The sparse round of a symmetric graph: chunk size and column type from the frontier, PRUNE from
@@ -1520,6 +1680,9 @@ int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, 
     // tail, or at the first round of a stepper run.
     if (clear_due(t) && !(cleared_for && *cleared_for == t))
         SW_HIP(hipMemsetAsync(f.act[(t + 1) & 1], 0, act_bytes(f.n_all), s));
+    SW_ARG(list_mask_compiled(tuning().list_mask),
+           "SWARM_LIST_* / SWARM_FLUSH_*: this combination of list-phase levers is not compiled (none, all, the "
+           "default, or -DSWARM_LIST_EXTRA=mask)");
     unsigned flags = 0;
     if (tuning().clear_inline && cleared_for && clear_due(t + 1)) {  // this round is that buffer's last reader
         flags |= SF_CLEAR;
