@@ -82,4 +82,22 @@ int launch_physics_loop_sensed(int64_t n, const int32_t *ids, const uint2 *rec, 
                                const double *obstacles, const LoopSense &ls, double dt, double max_speed,
                                unsigned long long *singular, hipStream_t s);
 
+// What a kernel reads of an obstacle field (contract O1; swarm_obstacle_field in swarm_common.h): the grid's
+// origin and shape, the cells' offsets and the cell lists as packed (x, y, r) triples.
+struct ObsFieldView {
+    const uint32_t *off;  // ncx * ncy + 1
+    const double *tri;    // 3 doubles per listed obstacle
+    double xmin, ymin, inv_cell;
+    int64_t ncx, ncy;
+};
+inline ObsFieldView obstacle_field_view(const swarm_obstacle_field &f) {
+    return {f.cell_off, f.tri, f.g.xmin, f.g.ymin, f.g.inv_cell, f.g.ncx, f.g.ncy};
+}
+// launch_physics_loop_sensed with the flat obstacle list replaced by the agent's cell list of a field: the
+// same bits (contract O1), no LDS and no barriers.
+int launch_physics_loop_sensed_field(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec,
+                                     double *pos_out, double *vel, double *target, uint8_t *has_target,
+                                     const ObsFieldView &field, const LoopSense &ls, double dt, double max_speed,
+                                     unsigned long long *singular, hipStream_t s);
+
 }  // namespace swarm

@@ -633,7 +633,135 @@ __global__ __launch_bounds__(kBlock) void k_physics_loop_sensed(
     count_singular(sing, singular);
 }
 
+// ---- obstacle fields (contract O1): a moving agent visits only the obstacles in its reach ----
+//
+// The field forms of k_physics_sensed and k_physics_loop_sensed: obstacle_forces(s_obs, ...) replaced by the
+// agent's own cell of the field's grid, two offset loads and a walk over that cell's (x, y, r) triples, read at
+// the cursor with no index indirection.  obstacle_term is the flat loop's body, statement for statement, and a
+// cell's triples are in list order; an obstacle that is not in the agent's cell list fails the flat loop's
+// pre-test for that agent (obstacle_cells.h has the proof), where it adds nothing, not even +0.0 -- so frx, fry
+// and the singular count keep the flat list's bits.  No s_obs, no LDS, no barriers, and an agent that does not
+// move reads nothing of the field.  Threads are in cell-sorted order and a field's cells are at least 10 units
+// wide (obstacle_cells.h, obs_start_side), against sensing cells of 1 or 2: the lanes of a wave mostly walk the
+// same one or two lists, so a load serves many lanes.
+// Bounds: cell_coord clamps both coordinates into [0, nc - 1] (NaN: 0), so c is in [0, ncx * ncy - 1];
+// off has ncx * ncy + 1 entries, ascending, the last one the number of triples (< 2^32): every q read is a
+// triple of the buffer.
+#ifndef SWARM_OBS_DEPTH
+#define SWARM_OBS_DEPTH 2
+#endif
+constexpr int kObsDepth = SWARM_OBS_DEPTH;  // triples in flight per thread
+
+__device__ __forceinline__ void obstacle_term(double ox, double oy, double r, double px, double py, double &frx,
+                                              double &fry, unsigned long long &sing) {
+    const double ex = px - ox, ey = py - oy;
+    const double s2 = ex * ex + ey * ey;
+    const double rr = 5.0 + r;
+    if (s2 > rr * rr * (1.0 + 1e-12)) return;  // the flat loop's pre-test (its `continue`)
+    double d = sqrt(s2) - r;
+    if (d <= 0.001) d = 0.001;
+    if (d < 5.0) {
+        const double mag = 50.0 * (1.0 / d - 1.0 / 5.0) / (d * d);
+        const double nrm = sqrt(s2);
+        sing += nrm == 0.0;
+        frx += (ex / nrm) * mag;
+        fry += (ey / nrm) * mag;
+    }
+}
+
+__device__ __forceinline__ void field_forces(const ObsFieldView &f, double px, double py, double &frx, double &fry,
+                                             unsigned long long &sing) {
+    const int64_t cx = cell_coord(px, f.xmin, f.inv_cell, f.ncx);
+    const int64_t cy = cell_coord(py, f.ymin, f.inv_cell, f.ncy);
+    const int64_t c = cy * f.ncx + cx;
+    const uint32_t e = f.off[c + 1];
+    for (uint32_t q = f.off[c]; q < e; q += kObsDepth) {
+        double t[kObsDepth][3];
+#pragma unroll
+        for (int u = 0; u < kObsDepth; ++u) {
+            const bool in = e - q > uint32_t(u);
+            const double *p = f.tri + 3 * size_t(in ? q + u : q);
+            t[u][0] = p[0], t[u][1] = p[1], t[u][2] = p[2];
+        }
+#pragma unroll
+        for (int u = 0; u < kObsDepth; ++u)
+            if (e - q > uint32_t(u)) obstacle_term(t[u][0], t[u][1], t[u][2], px, py, frx, fry, sing);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_physics_sensed_field(
+    int64_t n, const int32_t *__restrict__ ids, const uint8_t *__restrict__ state, const int32_t *__restrict__ leader,
+    const double2 *__restrict__ pin, double2 *__restrict__ pout, double2 *__restrict__ vel, double2 *__restrict__ tgt,
+    uint8_t *__restrict__ has_t, ObsFieldView field, Grid g, double r2, const int32_t *__restrict__ sorted_idx,
+    const uint32_t *__restrict__ off, const double2 *__restrict__ psort, double dt, double max_speed,
+    unsigned long long *__restrict__ st) {
+    const bool stopped = st[0] != 0;  // uniform over the grid: written by an earlier kernel of the stream
+    unsigned long long sing = 0;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        if (stopped) {
+            pout[q0] = pin[q0];
+            continue;
+        }
+        const int64_t i = sorted_idx[q0];
+        const double2 p = psort[q0];
+        const double px = p.x, py = p.y;
+        double2 t;
+        if (!formation_target(i, ids, state, leader, pin, tgt, has_t, t)) {
+            pout[i] = make_double2(px, py);
+            continue;
+        }
+        double frx = 0.0, fry = 0.0;
+        field_forces(field, px, py, frx, fry, sing);
+        double fax = 0.0, fay = 0.0;
+        attraction(px, py, t, fax, fay);
+        const SepAcc sep = window_separation(i, px, py, g, r2, sorted_idx, off, psort, sing);
+        sing = sep.sing;
+        integrate(i, px, py, fax, fay, frx, fry, sep.x, sep.y, dt, max_speed, vel, pout);
+    }
+    count_singular(sing, st + 1);
+}
+
+__global__ __launch_bounds__(kBlock) void k_physics_loop_sensed_field(
+    int64_t n, const int32_t *__restrict__ ids, const uint2 *__restrict__ rec, const LRec *__restrict__ lrec,
+    double2 *__restrict__ pout, double2 *__restrict__ vel, double2 *__restrict__ tgt, uint8_t *__restrict__ has_t,
+    ObsFieldView field, Grid g, double r2, const int32_t *__restrict__ sorted_idx, const uint32_t *__restrict__ off,
+    const double2 *__restrict__ psort, double dt, double max_speed, const unsigned long long *__restrict__ st,
+    unsigned long long *__restrict__ singular) {
+    if (st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    unsigned long long sing = 0;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const int64_t i = sorted_idx[q0];
+        const double2 p = psort[q0];
+        const double px = p.x, py = p.y;
+        double2 t;
+        if (!formation_target_loop(i, ids, rec[i].x, lrec, tgt, has_t, t)) {
+            pout[i] = make_double2(px, py);  // dead or without a target: its position in the output buffer too
+            continue;
+        }
+        double frx = 0.0, fry = 0.0;
+        field_forces(field, px, py, frx, fry, sing);
+        double fax = 0.0, fay = 0.0;
+        attraction(px, py, t, fax, fay);
+        const SepAcc sep = window_separation(i, px, py, g, r2, sorted_idx, off, psort, sing);
+        sing = sep.sing;
+        integrate(i, px, py, fax, fay, frx, fry, sep.x, sep.y, dt, max_speed, vel, pout);
+    }
+    count_singular(sing, singular);
+}
+
 }  // namespace
+
+int launch_physics_loop_sensed_field(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec,
+                                     double *pos_out, double *vel, double *target, uint8_t *has_target,
+                                     const ObsFieldView &field, const LoopSense &ls, double dt, double max_speed,
+                                     unsigned long long *singular, hipStream_t s) {
+    hipLaunchKernelGGL(k_physics_loop_sensed_field, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids, rec,
+                       lrec, reinterpret_cast<double2 *>(pos_out), reinterpret_cast<double2 *>(vel),
+                       reinterpret_cast<double2 *>(target), has_target, field, ls.g, ls.r2, ls.sorted, ls.off, ls.psort,
+                       dt, max_speed, ls.st, singular);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
 
 int launch_physics_loop(int64_t n, const int32_t *ids, const uint2 *rec, const LRec *lrec, const double *pos_in,
                         double *pos_out, double *vel, double *target, uint8_t *has_target, int64_t m,
@@ -789,15 +917,23 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
     unsigned long long *h = static_cast<unsigned long long *>(pinned(ctx, 64));
     if (!h) return SWARM_ERR_OOM;
     double2 *buf[2] = {reinterpret_cast<double2 *>(pos), other};
+    // `obstacles` that is a live field's own list: the field's path (contract O1: the same bits)
+    const swarm_obstacle_field *fld = find_obstacle_field(ctx, m, obstacles);
     // a refused step sets the stop word (ls.st[0]): it and every later step only copy the positions through
     auto queue_step = [&](int32_t k) -> int {
         const double2 *pin = buf[k & 1];
         const int rc = loop_sense_tick(ctx, n, reinterpret_cast<const double *>(pin), k, &ls, s, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_physics_sensed, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids, state,
-                           leader_index, pin, buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel),
-                           reinterpret_cast<double2 *>(target), has_target, m, obstacles, ls.g, ls.r2, ls.sorted,
-                           ls.off, ls.psort, dt, max_speed, ls.st);
+        if (fld)
+            hipLaunchKernelGGL(k_physics_sensed_field, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids,
+                               state, leader_index, pin, buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel),
+                               reinterpret_cast<double2 *>(target), has_target, obstacle_field_view(*fld), ls.g, ls.r2,
+                               ls.sorted, ls.off, ls.psort, dt, max_speed, ls.st);
+        else
+            hipLaunchKernelGGL(k_physics_sensed, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids, state,
+                               leader_index, pin, buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel),
+                               reinterpret_cast<double2 *>(target), has_target, m, obstacles, ls.g, ls.r2, ls.sorted,
+                               ls.off, ls.psort, dt, max_speed, ls.st);
         SW_LAUNCHED();
         return SWARM_OK;
     };

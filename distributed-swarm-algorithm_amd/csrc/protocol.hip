@@ -1710,7 +1710,12 @@ struct TickClocks {
 int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t, double **cur, double **lag,
                  unsigned long long *sing, hipStream_t s) {
     const LoopArgs *loop = r.loop;
-    const int rc = r.sensed() ? launch_physics_loop_sensed(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
+    // `obstacles` that is a live field's own list: the sensed loops take the field's path (contract O1)
+    const swarm_obstacle_field *fld = r.sensed() ? find_obstacle_field(r.ctx, loop->m, loop->obstacles) : nullptr;
+    const int rc = fld        ? launch_physics_loop_sensed_field(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
+                                                                 loop->has_target, obstacle_field_view(*fld), ls, r.dt,
+                                                                 loop->max_speed, sing, s)
+                   : r.sensed() ? launch_physics_loop_sensed(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
                                                            loop->has_target, loop->m, loop->obstacles, ls, r.dt,
                                                            loop->max_speed, sing, s)
                               : launch_physics_loop(r.n, r.ids, f.rec, f.lrec, *cur, *lag, loop->vel, loop->target,

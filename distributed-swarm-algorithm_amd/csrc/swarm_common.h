@@ -89,7 +89,20 @@ struct AucPersist {
 };
 }  // namespace swarm
 
+// An obstacle field (contract O1; obstacle_field.hip builds it, physics.hip reads it).  Everything it points to
+// is owned by the field until swarm_obstacle_field_destroy (or its ctx's destroy).
+struct swarm_obstacle_field {
+    int64_t m = 0;
+    double *obs = nullptr;         // device: the field's own copy of the list, m x 3 (the key of find_obstacle_field)
+    uint32_t *cell_off = nullptr;  // device: ncx * ncy + 1
+    double *tri = nullptr;         // device: the cell lists as packed (x, y, r) triples, in list order
+    swarm::Grid g{};
+    std::vector<uint32_t> cell_off_host;
+    std::vector<int32_t> idx_host;  // the cell lists as obstacle indices (swarm_obstacle_field_read)
+};
+
 struct swarm_ctx {
+    std::vector<swarm_obstacle_field *> fields;  // the live obstacle fields created on this ctx
     swarm::AucPersist auc;         // sharded auction between begin and the round calls
     int device = 0;
     void *slot[swarm::S_NUM] = {};
@@ -147,6 +160,18 @@ void *mapped(swarm_ctx *ctx, size_t bytes, void **dev);
 // start from a cold core); hipStreamQuery every 256 spins reports a failed stream, and a stream that
 // finished without the write is an error.
 int wait_mapped_word(const unsigned long long *w, unsigned long long v, hipStream_t s, const char *what);
+
+// The live field of ctx whose own list `obstacles` is (exactly its pointer, with its m), or NULL: any other
+// pointer is a flat list.  The key is memory the library owns until the field is destroyed, so no allocator can
+// hand it to somebody else while the field lives.
+inline const swarm_obstacle_field *find_obstacle_field(const swarm_ctx *ctx, int64_t m, const double *obstacles) {
+    if (obstacles)
+        for (const swarm_obstacle_field *f : ctx->fields)
+            if (f->obs == obstacles && f->m == m) return f;
+    return nullptr;
+}
+// Frees a field's memory (the caller has taken it off its ctx's list and made sure the device is done with it).
+void free_obstacle_field(swarm_obstacle_field *f);
 
 }  // namespace swarm
 

@@ -1,7 +1,8 @@
 """swarm_amd -- MI355X-native batched swarm step (leader election + task allocation).
 
 Public surface:
-  Swarm, ElectResult, AllocResult   batched HBM-resident swarm (swarm.py), HIP kernels via
+  Swarm, ElectResult, AllocResult, ObstacleField
+                                    batched HBM-resident swarm (swarm.py), HIP kernels via
                                     libswarm.so (include/swarm.h)
   gen                               seeded synthetic inputs
   dist                              multi-GPU sharded election / allocation (torch.distributed)
@@ -9,11 +10,11 @@ The scalar drop-in for the reference's `agent` module lives next to this package
 """
 from . import gen  # noqa: F401  (numpy-only; importable without a GPU)
 
-__all__ = ["gen", "Swarm", "ElectResult", "AllocResult"]
+__all__ = ["gen", "Swarm", "ElectResult", "AllocResult", "ObstacleField"]
 
 
 def __getattr__(name):  # lazy: importing swarm_amd does not initialise HIP
-    if name in ("Swarm", "ElectResult", "AllocResult"):
+    if name in ("Swarm", "ElectResult", "AllocResult", "ObstacleField"):
         from . import swarm
         return getattr(swarm, name)
     raise AttributeError(name)

@@ -38,7 +38,9 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_comm_unique_id_kind", "swarm_comm_create_kind", "swarm_comm_kind", "swarm_allocate_indexed_ex",
            "swarm_protocol_run_ex", "swarm_elect_sharded_ex", "swarm_graph_compact_escaped",
            "swarm_frontier_set_compact_escaped", "swarm_physics_run_sensed", "swarm_update_loop",
-           "swarm_update_loop_sensed", "swarm_update_loop_radio", "swarm_update_loop_tasks")
+           "swarm_update_loop_sensed", "swarm_update_loop_radio", "swarm_update_loop_tasks",
+           "swarm_obstacle_field_create", "swarm_obstacle_field_obstacles", "swarm_obstacle_field_read",
+           "swarm_obstacle_field_destroy")
 
 
 class SwarmError(RuntimeError):
@@ -57,6 +59,13 @@ class Tasks(ctypes.Structure):
     _fields_ = [("T", ctypes.c_int32)] + \
                [(k, ctypes.c_void_p) for k in ("tpos", "treq", "caps", "status_lo", "status_hi", "claim_out",
                                                "conflict_out", "tab_winner", "tab_util")]
+
+
+class ObstacleFieldInfo(ctypes.Structure):
+    """swarm_obstacle_field_info."""
+    _fields_ = [("m", ctypes.c_int64), ("live", ctypes.c_int64), ("ncx", ctypes.c_int64), ("ncy", ctypes.c_int64),
+                ("cell", ctypes.c_double), ("xmin", ctypes.c_double), ("ymin", ctypes.c_double),
+                ("pairs", ctypes.c_int64), ("longest", ctypes.c_int64)]
 
 
 class AllocStats(ctypes.Structure):
@@ -192,6 +201,10 @@ def load(path: str = LIB_PATH):
                                             ctypes.POINTER(i32), P, P, P]
         L.swarm_auction.argtypes = [P, i64, P, P, P, i64, P, P, d, d, ctypes.c_float, i32, P, P, P,
                                     ctypes.POINTER(i32), P, P, P]
+        L.swarm_obstacle_field_create.argtypes = [P, i64, P, ctypes.POINTER(P), ctypes.POINTER(ObstacleFieldInfo), P]
+        L.swarm_obstacle_field_obstacles.argtypes = [P, ctypes.POINTER(P)]
+        L.swarm_obstacle_field_read.argtypes = [P, P, P]
+        L.swarm_obstacle_field_destroy.argtypes = [P, P]
         for name in EXPORTS:
             if name not in ("swarm_last_error", "swarm_version"):
                 getattr(L, name).restype = ctypes.c_int

@@ -117,6 +117,86 @@ def take_rows(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return torch.stack([t[:, j].contiguous()[idx] for j in range(t.shape[1])], 1).contiguous()
 
 
+def _destroy_field(ctx, handle):
+    """ObstacleField's finalizer: `ctx` is held so that the ctx outlives its field (a ctx on another device
+    than the current one refuses the call: its own device is made current for it)."""
+    L = _lib._lib
+    if L is not None and handle.value and ctx.handle.value:
+        with torch.cuda.device(ctx.device):
+            L.swarm_obstacle_field_destroy(ctx.handle, handle)
+    handle.value = None
+
+
+class ObstacleField:
+    """An obstacle field (contract O1, swarm_obstacle_field): a list of m obstacles (x, y, r) with, per cell
+    of a grid over them, the obstacles that can act on an agent there.  Made by Swarm.obstacle_field();
+    read-only.  Pass it wherever an `obstacles=` list goes: the sensed calls (physics_step with sense_radius,
+    update_loop_sensed / _radio / _tasks) then visit only the obstacles in an agent's reach, the fixed-graph
+    calls read its list -- every result bit-identical to the same call with the list.  The field belongs to
+    the calling thread's ctx of its device; from another thread the calls read it as the flat list."""
+
+    def __init__(self, obstacles, device):
+        import weakref
+        dev = device if isinstance(device, torch.device) else _dev(device)
+        # (always a copy: later writes to the caller's tensor must not reach the field)
+        src = torch.tensor(np.asarray(obstacles.detach().cpu() if isinstance(obstacles, torch.Tensor) else obstacles,
+                                      dtype=np.float64).reshape(-1, 3))
+        self.obstacles = src.numpy().copy()
+        self.obstacles.flags.writeable = False
+        self.m, self.device = int(src.shape[0]), dev
+        info, self._handle = _lib.ObstacleFieldInfo(), ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            d_obs = src.to(dev)
+            self._ctx = _lib.ctx()
+            _lib.check(_lib.lib().swarm_obstacle_field_create(
+                self._ctx, self.m, _lib.ptr(d_obs) if self.m else None, ctypes.byref(self._handle),
+                ctypes.byref(info), _lib.stream()))
+        self.info = {k: getattr(info, k) for k, _ in _lib.ObstacleFieldInfo._fields_}
+        self._ptr = ctypes.c_void_p()
+        _lib.check(_lib.lib().swarm_obstacle_field_obstacles(self._handle, ctypes.byref(self._ptr)))
+        self._finalizer = weakref.finalize(self, _destroy_field, self._ctx, self._handle)
+
+    @property
+    def closed(self) -> bool:
+        return not self._finalizer.alive
+
+    def _check_open(self):
+        if self.closed:
+            raise ValueError("the obstacle field is closed")
+
+    def read(self):
+        """(cell_off uint32 [ncx * ncy + 1], idx int32 [pairs]): cell c = cy * ncx + cx lists the obstacles
+        idx[cell_off[c]:cell_off[c + 1]], ascending."""
+        self._check_open()
+        off = np.zeros(self.info["ncx"] * self.info["ncy"] + 1, np.uint32)
+        idx = np.zeros(self.info["pairs"], np.int32)
+        _lib.check(_lib.lib().swarm_obstacle_field_read(self._handle, off.ctypes.data_as(ctypes.c_void_p),
+                                                        idx.ctypes.data_as(ctypes.c_void_p)))
+        return off, idx
+
+    def close(self):
+        """Frees the field (waits for the device first).  Using it afterwards raises ValueError."""
+        if not self.closed:
+            with torch.cuda.device(self.device):
+                self._finalizer()
+
+    def _args(self, dev):
+        """(m, device pointer of the field's own list) for a call on device `dev`."""
+        self._check_open()
+        if dev != self.device:
+            raise ValueError(f"the obstacle field lives on {self.device}, the swarm on {dev}")
+        return self.m, self._ptr
+
+
+def _obstacle_args(obstacles, dev):
+    """(m, pointer or None, keep-alive) of an `obstacles=` argument: a list or an ObstacleField."""
+    if isinstance(obstacles, ObstacleField):
+        return (*obstacles._args(dev), obstacles)
+    obs = torch.zeros((0, 3), dtype=torch.float64, device=dev) if obstacles is None else \
+        _to(obstacles, torch.float64, dev).reshape(-1, 3).contiguous()
+    return obs.shape[0], (_lib.ptr(obs) if obs.numel() else None), obs
+
+
 class Swarm:
     """Structure-of-arrays swarm resident on one GPU."""
 
@@ -551,6 +631,13 @@ class Swarm:
             cand = torch.where(ok, idx[leader.clamp(0, idx.numel() - 1).long()], out)
         return torch.where(self.state == _lib.FOLLOWER, cand, out).contiguous()
 
+    def obstacle_field(self, obstacles) -> ObstacleField:
+        """An ObstacleField of the (m, 3) [x, y, r] list on this swarm's device (contract O1, DESIGN 4j;
+        swarm_obstacle_field_create).  The list is copied.  Built on the host, once; every `obstacles=`
+        parameter accepts the field.  SwarmError: ERR_ARG for a non-finite entry or footprints without a finite
+        extent, ERR_RANGE for more than 2^26 (cell, obstacle) pairs."""
+        return ObstacleField(obstacles, self.device)
+
     def physics_step(self, obstacles=None, *, sensors=None, leader_index=None, dt: float = 0.1,
                      max_speed: float = 5.0, steps: int = 1, sense_radius: float | None = None) -> dict:
         """`steps` synchronous _update_physics steps (agent.py:94-181) of every agent, in place on
@@ -570,8 +657,7 @@ class Swarm:
             self.vel = torch.zeros((n, 2), dtype=torch.float64, device=dev)
             self.target = torch.zeros((n, 2), dtype=torch.float64, device=dev)
             self.has_target = torch.zeros(n, dtype=torch.uint8, device=dev)
-        obs = torch.zeros((0, 3), dtype=torch.float64, device=dev) if obstacles is None else \
-            _to(obstacles, torch.float64, dev).reshape(-1, 3).contiguous()
+        obs_m, obs_ptr, _obs_keep = _obstacle_args(obstacles, dev)
         if sense_radius is not None:
             li = self.leader_index() if leader_index is None else _to(leader_index, torch.int32, dev)
             sing, done = ctypes.c_int64(0), ctypes.c_int32(0)
@@ -579,7 +665,7 @@ class Swarm:
             with torch.cuda.device(dev):
                 rc = _lib.lib().swarm_physics_run_sensed(
                     _lib.ctx(), n, p(self.ids), p(self.state), p(li), p(self.pos), p(self.vel), p(self.target),
-                    p(self.has_target), obs.shape[0], _lib.ptr(obs) if obs.numel() else None, float(sense_radius),
+                    p(self.has_target), obs_m, obs_ptr, float(sense_radius),
                     int(steps), float(dt), float(max_speed), ctypes.byref(done), ctypes.byref(sing), _lib.stream())
             self.last_steps_done = done.value
             if done.value:
@@ -599,7 +685,7 @@ class Swarm:
                 _lib.check(_lib.lib().swarm_physics_step(
                     _lib.ctx(), n, _lib.ptr(self.ids), _lib.ptr(self.state), _lib.ptr(li), _lib.ptr(self.pos),
                     _lib.ptr(other), _lib.ptr(self.vel), _lib.ptr(self.target), _lib.ptr(self.has_target),
-                    obs.shape[0], _lib.ptr(obs) if obs.numel() else None, _lib.ptr(rp), _lib.ptr(col) if col.numel() else None,
+                    obs_m, obs_ptr, _lib.ptr(rp), _lib.ptr(col) if col.numel() else None,
                     float(dt), float(max_speed), ctypes.byref(sing), _lib.stream()))
                 total += sing.value
                 self.pos, other = other, self.pos
@@ -901,8 +987,7 @@ class Swarm:
                 (_to(sensors[0], torch.int32, dev), _to(sensors[1], torch.int32, dev))
             if srp.numel() != n + 1:
                 raise ValueError(f"sensors: row_ptr needs {n + 1} entries, got {srp.numel()}")
-        obs = torch.zeros((0, 3), dtype=torch.float64, device=dev) if obstacles is None else \
-            _to(obstacles, torch.float64, dev).reshape(-1, 3).contiguous()
+        obs_m, obs_ptr, _obs_keep = _obstacle_args(obstacles, dev)
         k = getattr(self, "_pos_prev_key", None)
         if k is None or k[0] is not self.pos or k[1] != self.pos._version or not hasattr(self, "pos_prev"):
             self.pos_prev = self.pos.clone()
@@ -926,8 +1011,7 @@ class Swarm:
                 (_lib.ptr(self.row_ptr, torch.int32), _lib.ptr(self.col, torch.int32) if self.n_edges else None, *hear)
             run = (p(self.tick_off), ctypes.byref(fs), self.fsm_tick, ticks, float(dt), float(timeout), float(jitter),
                    ctypes.c_uint64(int(seed)), kt.ctypes.data_as(ctypes.c_void_p) if kt.size else None, kt.size)
-            motion = (p(self.vel), p(self.target), p(self.has_target), obs.shape[0],
-                      _lib.ptr(obs) if obs.numel() else None)
+            motion = (p(self.vel), p(self.target), p(self.has_target), obs_m, obs_ptr)
             head = (_lib.ctx(), n, p(self.ids), p(self.pos), p(self.pos_prev), *graph, *run,
                     *(() if radio_radius is not None else (float(pull_frac) if mode == "hybrid" else -1.0,)), *motion)
             tail = (float(max_speed), _lib.ptr(trace) if frames and n else None, trace_every,

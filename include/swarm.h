@@ -746,6 +746,59 @@ int swarm_update_loop_tasks(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             int64_t *refused_tick, const swarm_tasks *tasks, int64_t *task_counts,
                             int64_t *n_guard, void *stream);
 
+/*
+ * Obstacle fields (contract O1): the sensed physics visits only the obstacles in reach.
+ * A field is built once from a list of m obstacles (x, y, r) and is read-only afterwards.  It owns a device
+ * copy of the list and, over a uniform grid that covers the obstacles' footprints, for every cell the
+ * obstacles that can act on an agent in that cell, stored as packed (x, y, r) triples in list order.  An
+ * obstacle acts only within 5 + r of its centre; it is listed in every cell its square of half side
+ * (5 + r)(1 + 1e-9) touches, so an agent that visits its own cell's list, in list order, evaluates every term
+ * the flat list's loop evaluates, in the same order: every output of a call given the field is bit-identical to
+ * the same call given the same m obstacles as a flat list (the loop's far-obstacle test skips the others
+ * without adding anything).  An obstacle with r <= -5 never acts and is in no list.
+ *
+ * Selection: no signature changes.  Pass m = the field's m and obstacles = the field's own list (the device
+ * pointer swarm_obstacle_field_obstacles stores in *obstacles; every function here returns a status) to any
+ * entry point that takes `m, obstacles`.  swarm_physics_run_sensed, swarm_update_loop_sensed,
+ * swarm_update_loop_radio and swarm_update_loop_tasks recognise exactly that pointer with that m, on the ctx the
+ * field was created on, and take the field's path: no LDS staging, no barriers, nothing done for an agent that
+ * does not move.  Any other pointer (a copy of the list, an offset into it, another m) is a flat list and takes
+ * the flat path.  swarm_physics_step and swarm_update_loop (fixed graphs) read the pointer as the flat list it
+ * also is: the same bits by the contract.  The key is memory the library owns until the field is destroyed.
+ *
+ * swarm_obstacle_field_create: obstacles (device, m x 3 f64, may be NULL when m == 0) is copied; the lists are
+ * built on the host, so the call waits for the stream once.  *info (may be NULL) describes the field.
+ * SWARM_ERR_ARG, nothing created: a NULL ctx or out, m outside [0, 2^31), a NaN or infinite entry, footprints
+ * whose bounding box has no finite extent.  SWARM_ERR_RANGE, nothing created: more than 2^26 (cell, obstacle)
+ * pairs -- counted by arithmetic before any list is allocated, so that a few huge obstacles among many small
+ * ones cannot fill memory.  The grid has at most 4 live + 1024 cells of side >= 10 (1 + 1e-9), whatever the radii:
+ * obstacles whose reach spans very many such cells are what the pair limit refuses -- give those as a flat list.
+ * swarm_obstacle_field_read (for tests and tools): cell_off_host (ncx * ncy + 1 u32) and idx_host (pairs i32,
+ * the lists as obstacle indices, ascending in every cell; cell c = cy * ncx + cx holds
+ * idx[cell_off[c] .. cell_off[c + 1])); either may be NULL.
+ * swarm_obstacle_field_destroy waits for the device, then frees the field; swarm_ctx_destroy frees the fields
+ * still alive.  A field must not be used after either.
+ */
+typedef struct swarm_obstacle_field swarm_obstacle_field;
+
+typedef struct {
+    int64_t m;       /* obstacles in the list */
+    int64_t live;    /* those with 5 + r > 0 */
+    int64_t ncx;     /* the grid: ncx x ncy cells of side `cell` from (xmin, ymin) */
+    int64_t ncy;
+    double cell;
+    double xmin;
+    double ymin;
+    int64_t pairs;   /* (cell, obstacle) pairs: the length of all lists together */
+    int64_t longest; /* the longest cell list */
+} swarm_obstacle_field_info;
+
+int swarm_obstacle_field_create(swarm_ctx *ctx, int64_t m, const double *obstacles, swarm_obstacle_field **out,
+                                swarm_obstacle_field_info *info, void *stream);
+int swarm_obstacle_field_obstacles(const swarm_obstacle_field *field, const double **obstacles);
+int swarm_obstacle_field_read(const swarm_obstacle_field *field, uint32_t *cell_off_host, int32_t *idx_host);
+int swarm_obstacle_field_destroy(swarm_ctx *ctx, swarm_obstacle_field *field);
+
 #ifdef __cplusplus
 }
 #endif
