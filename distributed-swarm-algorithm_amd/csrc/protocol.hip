@@ -42,9 +42,11 @@
 // (U1-S) senses every tick's separation neighbours from the tick's snapshot (k_physics_loop_sensed), and a
 // refused tick makes the call restore every caller array on the device (k_restore_refused: all or nothing).
 // swarm_update_loop_radio (U1-R) is the sensed loop without a message graph: k_tick_radio is k_tick_pull's
-// agent with the row walk replaced by the merge over its 3 x 3 cell window of the same binning.
+// agent with the row walk replaced by the receive over its 3 x 3 cell window of the same binning (hear_window).
 // swarm_update_loop_tasks (U1-T) is the radio loop with _process_tasks and the two task handlers run every tick:
-// k_radio_outbox_tasks, k_task_conflicts and k_tick_radio_tasks in place of the two radio kernels (TaskState).
+// k_radio_outbox<true>, k_task_conflicts and k_tick_radio_tasks in place of the two radio kernels (TaskState).
+// The four tick kernels (k_tick_pull, k_tick, k_tick_radio, k_tick_radio_tasks) differ in how an agent receives;
+// what follows the receive is one function (settle_agent), and the two window kernels share the receive too.
 // The host loop of all six entry points is run_ticks, a sequence of stages that each own their scratch:
 // check_run_args, Counters, pack_records, PushState / RadioState / TaskState / launch_tick_pull (the receive launch by
 // mode), EntrySnapshot (sensed), TickClocks (A/B aid), tick_physics, read_back (one host wait).
@@ -60,6 +62,7 @@ namespace swarm {
 namespace {
 
 constexpr uint8_t kAcclaim = 1, kHeartbeat = 2;
+constexpr uint8_t kClaim = 4, kConflict = 8;  // U1-T's sender bytes: the outbox bits and these two
 constexpr int kRecv = 8;  // CSR entries loaded per receive chunk (pull mode, hearer walks)
 // k_tick's row walks (75 VGPRs, 6 waves per SIMD; 4 entries per chunk: 63 VGPRs, 8 waves, but
 // 0.135 against 0.128 ms per tick -- the walks' chunks one after the other cost more than the
@@ -329,6 +332,30 @@ __global__ __launch_bounds__(kBlock) void k_sum_counts(int64_t ticks, const unsi
     }
 }
 
+struct TickCounts {
+    unsigned lead = 0, wait = 0, acc = 0, hb = 0;
+    unsigned single = 0, multi = 0, edges = 0;  // one thread's, one tick: < 2^32 (32-bit: VGPRs)
+};
+
+// The end of every tick kernel's alive agent i, after what it heard (h; r0: its record at the start of the
+// tick, bits / y: after the receive): its timers, its record (written when it changed), its leader, the
+// tick's four counts.  Returns its sends; the outbox write is the caller's.
+__device__ __forceinline__ uint8_t settle_agent(int64_t i, Heard &h, uint2 r0, uint32_t bits, int32_t y, int64_t t,
+                                                double now, double timeout, double jitter, uint64_t seed,
+                                                const int32_t *__restrict__ ids, const Fsm &f, TickCounts &c) {
+    const int32_t ph = fw_phase(r0.x);
+    const uint8_t ob = uint8_t(h.ob | timers(i, h.st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
+                                             ph, f, bits, y));
+    const uint32_t fw1 = fw_make(h.st, 1, bits, ph);
+    if (fw1 != r0.x || uint32_t(y) != r0.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
+    if (h.lead_set) f.lrec[i].leader = h.lead;
+    c.lead += h.st == ST_L;
+    c.wait += h.st == ST_W;
+    c.acc += (ob & kAcclaim) != 0;
+    c.hb += (ob & kHeartbeat) != 0;
+    return ob;
+}
+
 // ---------------------------------------------------------------- pull mode: one fused launch
 __global__ __launch_bounds__(kBlock) void k_tick_pull(int64_t n, int64_t t, const int32_t *__restrict__ ids,
                                                      const double2 *__restrict__ pos, const int32_t *__restrict__ rp,
@@ -340,33 +367,21 @@ __global__ __launch_bounds__(kBlock) void k_tick_pull(int64_t n, int64_t t, cons
     if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const double now = double(t) * dt;
-    unsigned c_lead = 0, c_wait = 0, c_acc = 0, c_hb = 0;
+    TickCounts c;
     for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock) {
         const uint2 r = f.rec[i];
-        const uint32_t fw = r.x;
-        if (!fw_alive(fw)) {
+        if (!fw_alive(r.x)) {
             ob_out[i] = 0;
             continue;
         }
-        const uint8_t st0 = fw_state(fw);
-        const int32_t ph = fw_phase(fw);
-        uint32_t bits = fw_bits(fw);
+        uint32_t bits = fw_bits(r.x);
         int32_t y = int32_t(r.y);
-        Heard h{st0, 0, false, false, 0, -1};
-        receive_row<kRecv>(rp[i], rp[i + 1], col, ob_in, ids, ids[i], ((t + ph) % 10) == 0, h);
+        Heard h{fw_state(r.x), 0, false, false, 0, -1};
+        receive_row<kRecv>(rp[i], rp[i + 1], col, ob_in, ids, ids[i], ((t + fw_phase(r.x)) % 10) == 0, h);
         apply_heard(i, h, t, pos, f, bits, y);
-        const uint8_t ob = h.ob | timers(i, h.st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
-                                         ph, f, bits, y);
-        const uint32_t fw1 = fw_make(h.st, 1, bits, ph);
-        if (fw1 != fw || uint32_t(y) != r.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
-        if (h.lead_set) f.lrec[i].leader = h.lead;
-        ob_out[i] = ob;
-        c_lead += h.st == ST_L;
-        c_wait += h.st == ST_W;
-        c_acc += (ob & kAcclaim) != 0;
-        c_hb += (ob & kHeartbeat) != 0;
+        ob_out[i] = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
     }
-    add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
+    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
 }
 
 // ---------------------------------------------------------------- push mode
@@ -504,11 +519,6 @@ __device__ __forceinline__ int block_excl_scan(int c, int &total, int *s_wave) {
     return off + ex;
 }
 
-struct TickCounts {
-    unsigned lead = 0, wait = 0, acc = 0, hb = 0;
-    unsigned single = 0, multi = 0, edges = 0;  // one thread's, one tick: < 2^32 (32-bit: VGPRs)
-};
-
 // k_tick's own mail: once a workgroup's agents are done it mails the hearers of the senders it
 // listed, into tick t+1's words; the words are rotated over three buffers (tick t reads buf(t),
 // mails into buf(t+1) and clears buf(t+2), read in tick t-1 and next mailed in tick t+1) and the
@@ -526,25 +536,15 @@ struct NextMail {
     int64_t clk_t0;                  // SWARM_TICK_CLOCKS: the run's first tick
 };
 
-// Timers and writes of alive agent i after what it heard (h; r0: its record at the start of the tick,
-// bits / y: after the receive), its sends listed.
+// k_tick's agent: settle_agent, its outbox byte written when it differs from the slot's (prev: tick t-2's),
+// its sends listed.
 __device__ __forceinline__ void finish_agent(int64_t i, Heard &h, uint2 r0, uint32_t bits, int32_t y, uint8_t prev,
                                              int64_t t, double now, double timeout, double jitter, uint64_t seed,
                                              const int32_t *__restrict__ ids, const Fsm &f,
                                              uint8_t *__restrict__ ob_out, int32_t *seg, int *s_ns, TickCounts &c) {
-    uint8_t st = h.st;
-    const int32_t ph = fw_phase(r0.x);
-    const uint8_t ob = uint8_t(h.ob | timers(i, st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
-                                             ph, f, bits, y));
-    const uint32_t fw1 = fw_make(st, 1, bits, ph);
-    if (fw1 != r0.x || uint32_t(y) != r0.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
-    if (h.lead_set) f.lrec[i].leader = h.lead;
+    const uint8_t ob = settle_agent(i, h, r0, bits, y, t, now, timeout, jitter, seed, ids, f, c);
     if (ob != prev) ob_out[i] = ob;
     if (ob) seg[atomicAdd(s_ns, 1)] = int32_t(i);  // this workgroup's sender segment (LDS counter)
-    c.lead += st == ST_L;
-    c.wait += st == ST_W;
-    c.acc += (ob & kAcclaim) != 0;
-    c.hb += (ob & kHeartbeat) != 0;
 }
 
 // k_tick at >= 7 waves per SIMD (72 VGPRs, a few spilled): 0.1111 ms per tick against 0.1142 at 6 (79 VGPRs)
@@ -866,25 +866,38 @@ struct Radio {
     const unsigned long long *st;      // the call's verdict word: != 0, a tick was refused
 };
 
-__global__ __launch_bounds__(kBlock) void k_radio_outbox(int64_t n, const uint8_t *__restrict__ ob_in, Radio w) {
+// The outbox pass of both window loops.  U1-R (kTasks false): `in` is the inbound outbox, one cell plane.
+// U1-T: `in` is the inbound sender bytes (TaskTick::sb_in, below) -- the outbox bits plus kClaim / kConflict,
+// "the sender claimed", "the sender sent a conflict" -- and a cell plane for each of the three kinds of sender.
+template <bool kTasks>
+__global__ __launch_bounds__(kBlock) void k_radio_outbox(int64_t n, const uint8_t *__restrict__ in, Radio w,
+                                                        uint8_t *__restrict__ cell_claim,
+                                                        uint8_t *__restrict__ cell_conf) {
     if (w.st[0] != 0) return;
     for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n; q += int64_t(gridDim.x) * kBlock) {
-        const uint8_t o = ob_in[w.sorted[q]] & (kAcclaim | kHeartbeat);
+        const uint8_t o = kTasks ? in[w.sorted[q]] : in[w.sorted[q]] & (kAcclaim | kHeartbeat);
+        const uint8_t fsm = o & (kAcclaim | kHeartbeat);
+        const bool cl = kTasks && (o & kClaim) != 0, cf = kTasks && (o & kConflict) != 0;
         w.ob_sorted[q] = o;
         if (o) {  // (every writer of a cell's byte stores the same 1)
             const double2 p = w.psort[q];
             const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
             const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
-            w.cell_send[cy * w.g.ncx + cx] = 1;
+            const int64_t c = cy * w.g.ncx + cx;
+            if (fsm) w.cell_send[c] = 1;
+            if (cl) cell_claim[c] = 1;
+            if (cf) cell_conf[c] = 1;
         }
     }
 }
 
-// k_tick_pull's agent over the window: threads in cell-sorted order (a wave's lanes share their windows and
-// the nine sender bytes; the records are gathered by storage index), the Rc predicate on the cell-sorted
-// snapshot, ids[j] gathered only for a candidate that sent and is in range.  Three ways through a tick, all
-// exact:
-//   skip    a receiver whose nine cells hold no sender hears nothing and runs only its timers;
+// The window receive of both window loops: everything alive agent i (at p, storage index i) hears on the
+// tick's snapshot, the Rc predicate on the cell-sorted copy, the heard senders handed to `sender(o, sid, j)`
+// -- sorted outbox byte, ID, storage index -- in ascending storage index; ids[j] is gathered only for a
+// candidate that sent and is in range.  `flag(cell)`: whether the receiver listens to anything cell `cell`
+// holds (a cell plane's byte, or several OR-ed); `rel`: the bits of a sorted outbox byte it listens to.
+// Three ways through, all exact:
+//   skip    a receiver whose nine cells hold no such sender hears nothing;
 //   few     otherwise it scans the outbox bytes of the flagged cells only and keeps the heard senders' indices
 //           in a sorted register list of kHeardFast entries -- heartbeats come every tenth own tick from
 //           leaders only, so a window mostly holds one or two senders -- and handles them in ascending index;
@@ -893,9 +906,79 @@ __global__ __launch_bounds__(kBlock) void k_radio_outbox(int64_t n, const uint8_
 //           window_merge.h, every candidate in ascending index.
 // (The merge for every receiver with a flagged cell: 0.92 ms per tick at 10M agents against 0.64 in this form;
 // the list alone, a crowded window scanned first and merged after: 0.69.  DESIGN 4h.)
-// Returns at once when a tick of the call was refused (the caller restores every array).
 constexpr int kHeardFast = 4;
 constexpr int kHeardCells = 4;  // more window cells than this hold senders: no scan, the merge at once
+template <class Flag, class Sender>
+__device__ __forceinline__ void hear_window(double2 p, int64_t i, const Radio &w, uint8_t rel,
+                                            const int32_t *__restrict__ ids, Flag &&flag, Sender &&sender) {
+    const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+    const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+    unsigned cells = 0;  // bit k: window cell k holds a sender this receiver listens to (the bytes loaded at once)
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const WindowCell c = window_cell(w.g, cx, cy, k);
+        // (loaded ahead of the test: as `c.in && flag(c.at)` the nine loads wait for one another, and
+        // update_loop_radio takes 4.02 ms per tick for 3.98 at 10M agents)
+        const uint8_t fl = flag(c.at);
+        cells |= c.in && fl ? 1u << k : 0u;
+    }
+    if (!cells) return;
+    // senders all around (an election storm): the list would overflow, merge at once
+    const bool crowded = __popc(cells) > kHeardCells;
+    // the heard senders of the flagged cells, the kHeardFast lowest indices kept in ascending order (an
+    // insertion network on registers); one more than fit: the window is merged instead
+    int32_t sj[kHeardFast];
+    uint8_t so[kHeardFast];
+#pragma unroll
+    for (int u = 0; u < kHeardFast; ++u) {
+        sj[u] = kMergeEnd;
+        so[u] = 0;
+    }
+    bool more = crowded;
+    for (int k = 0; k < 9 && !crowded; ++k) {
+        if (!((cells >> k) & 1u)) continue;
+        const int64_t c = window_cell(w.g, cx, cy, k).at;
+        for (uint32_t q = w.off[c], e = w.off[c + 1]; q < e; ++q) {
+            uint8_t o = w.ob_sorted[q] & rel;
+            if (!o) continue;
+            int32_t j = w.sorted[q];
+            const double2 s = w.psort[q];
+            const double ex = p.x - s.x, ey = p.y - s.y;
+            if (j == int32_t(i) || !(ex * ex + ey * ey <= w.r2)) continue;
+#pragma unroll
+            for (int u = 0; u < kHeardFast; ++u) {
+                const bool lower = j < sj[u];
+                const int32_t tj = sj[u];
+                const uint8_t to = so[u];
+                sj[u] = lower ? j : tj;
+                so[u] = lower ? o : to;
+                j = lower ? tj : j;
+                o = lower ? to : o;
+            }
+            more |= j != kMergeEnd;  // an index fell off the end of the list
+        }
+    }
+    if (!more) {
+        int32_t ss[kHeardFast];  // the senders' IDs, all loads in flight
+#pragma unroll
+        for (int u = 0; u < kHeardFast; ++u) ss[u] = sj[u] != kMergeEnd ? ids[sj[u]] : 0;
+#pragma unroll
+        for (int u = 0; u < kHeardFast; ++u)
+            if (sj[u] != kMergeEnd) sender(so[u], ss[u], sj[u]);
+    } else {
+        window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
+            const uint8_t o = w.ob_sorted[q] & rel;
+            if (!o || j == int32_t(i)) return;
+            const double2 s = w.psort[q];
+            const double ex = p.x - s.x, ey = p.y - s.y;
+            if (ex * ex + ey * ey <= w.r2) sender(o, ids[j], j);
+        });
+    }
+}
+
+// k_tick_pull's agent over the window: threads in cell-sorted order (a wave's lanes share their windows and
+// the nine sender bytes; the records are gathered by storage index), the row walk replaced by hear_window.
+// Returns at once when a tick of the call was refused (the caller restores every array).
 __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, const int32_t *__restrict__ ids,
                                                       const double2 *__restrict__ pos, Fsm f, Radio w,
                                                       uint8_t *__restrict__ ob_out, double dt, double timeout,
@@ -906,110 +989,35 @@ __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, con
     if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const double now = double(t) * dt;
-    unsigned c_lead = 0, c_wait = 0, c_acc = 0, c_hb = 0;
+    TickCounts c;
     for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
         const int64_t i = w.sorted[q0];
         const uint2 r = f.rec[i];
-        const uint32_t fw = r.x;
-        if (!fw_alive(fw)) {
+        if (!fw_alive(r.x)) {
             ob_out[i] = 0;
             continue;
         }
         const double2 p = w.psort[q0];
         const int32_t me = ids[i];
-        const uint8_t st0 = fw_state(fw);
-        const int32_t ph = fw_phase(fw);
-        const bool hb_tick = ((t + ph) % 10) == 0;
-        uint32_t bits = fw_bits(fw);
+        const bool hb_tick = ((t + fw_phase(r.x)) % 10) == 0;
+        uint32_t bits = fw_bits(r.x);
         int32_t y = int32_t(r.y);
-        Heard h{st0, 0, false, false, 0, -1};
-        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
-        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
-        unsigned cells = 0;  // bit k: window cell k holds a sender (the nine bytes loaded at once)
-        uint8_t flag[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int64_t yy = cy + (k / 3) - 1, xx = cx + (k % 3) - 1;
-            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
-            flag[k] = w.cell_send[in ? yy * w.g.ncx + xx : 0];
-            cells |= in ? 1u << k : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) cells &= flag[k] ? ~0u : ~(1u << k);
-        // senders all around (an election storm): the list would overflow, merge at once
-        const bool crowded = __popc(cells) > kHeardCells;
-        if (cells) {
-            // the heard senders of the flagged cells, the kHeardFast lowest indices kept in ascending order
-            // (an insertion network on registers); one more than fit: the window is merged instead
-            int32_t sj[kHeardFast];
-            uint8_t so[kHeardFast];
-#pragma unroll
-            for (int u = 0; u < kHeardFast; ++u) {
-                sj[u] = kMergeEnd;
-                so[u] = 0;
-            }
-            bool more = crowded;
-            for (int k = 0; k < 9 && !crowded; ++k) {
-                if (!((cells >> k) & 1u)) continue;
-                const int64_t c = (cy + (k / 3) - 1) * w.g.ncx + cx + (k % 3) - 1;
-                for (uint32_t q = w.off[c], e = w.off[c + 1]; q < e; ++q) {
-                    uint8_t o = w.ob_sorted[q];
-                    if (!o) continue;
-                    int32_t j = w.sorted[q];
-                    const double2 s = w.psort[q];
-                    const double ex = p.x - s.x, ey = p.y - s.y;
-                    if (j == int32_t(i) || !(ex * ex + ey * ey <= w.r2)) continue;
-#pragma unroll
-                    for (int u = 0; u < kHeardFast; ++u) {
-                        const bool lower = j < sj[u];
-                        const int32_t tj = sj[u];
-                        const uint8_t to = so[u];
-                        sj[u] = lower ? j : tj;
-                        so[u] = lower ? o : to;
-                        j = lower ? tj : j;
-                        o = lower ? to : o;
-                    }
-                    more |= j != kMergeEnd;  // an index fell off the end of the list
-                }
-            }
-            if (!more) {
-                int32_t ss[kHeardFast];  // the senders' IDs, all loads in flight
-#pragma unroll
-                for (int u = 0; u < kHeardFast; ++u) ss[u] = sj[u] != kMergeEnd ? ids[sj[u]] : 0;
-#pragma unroll
-                for (int u = 0; u < kHeardFast; ++u)
-                    if (sj[u] != kMergeEnd) hear(h, so[u], ss[u], sj[u], me, hb_tick);
-            } else {
-                window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
-                    const uint8_t o = w.ob_sorted[q];
-                    if (!o || j == int32_t(i)) return;
-                    const double2 s = w.psort[q];
-                    const double ex = p.x - s.x, ey = p.y - s.y;
-                    if (ex * ex + ey * ey <= w.r2) hear(h, o, ids[j], j, me, hb_tick);
-                });
-            }
-        }
+        Heard h{fw_state(r.x), 0, false, false, 0, -1};
+        // (0xFF, not the two outbox bits: the pass wrote the byte masked, the `&` folds away)
+        hear_window(p, i, w, 0xFF, ids, [&](int64_t cell) { return w.cell_send[cell]; },
+                    [&](uint8_t o, int32_t sid, int32_t j) { hear(h, o, sid, j, me, hb_tick); });
         apply_heard(i, h, t, pos, f, bits, y);
-        const uint8_t ob = h.ob | timers(i, h.st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
-                                         ph, f, bits, y);
-        const uint32_t fw1 = fw_make(h.st, 1, bits, ph);
-        if (fw1 != fw || uint32_t(y) != r.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
-        if (h.lead_set) f.lrec[i].leader = h.lead;
-        ob_out[i] = ob;
-        c_lead += h.st == ST_L;
-        c_wait += h.st == ST_W;
-        c_acc += (ob & kAcclaim) != 0;
-        c_hb += (ob & kHeartbeat) != 0;
+        ob_out[i] = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
     }
-    add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
+    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
 }
 
 // ---------------------------------------------------------------- task update loop (contract U1-T)
 // U1-R's tick with _process_tasks and the two task handlers (agent.py:292-336), DESIGN 4i.  Per agent: a
 // 2-bit status per task (two 64-bit words), its claim table (a dense row of T winners and f32 utilities), and
 // by tick parity the set of tasks it claimed and the set it sent a TASK_CONFLICT on.  Three launches per tick,
-// none of them U1-R's kernels (those keep their instructions):
-//   k_radio_outbox_tasks  k_radio_outbox with two more bits in the cell-sorted byte -- the sender claimed, the
+// the receive and the agent's end shared with U1-R's kernels (hear_window, settle_agent):
+//   k_radio_outbox<true>  the outbox pass with two more bits in the cell-sorted byte -- the sender claimed, the
 //                         sender sent a conflict -- and a cell byte for each of the three kinds of sender; it
 //                         gathers one scratch byte per agent (TaskTick::sb_in), which the tick kernel wrote;
 //   k_task_conflicts      the tick's TASK_CONFLICT delivery, before the receive: it writes only the status,
@@ -1018,12 +1026,11 @@ __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, con
 //                         a task names the winner its table holds at the end of that tick's receive -- read
 //                         here from the sender's row, which no thread of this launch writes;
 //   k_tick_radio_tasks    k_tick_radio's agent with the claims of each heard sender handled right after its
-//                         election packets (LEADERs only, on all three paths), then the timers, then the claim
-//                         evaluation of the tasks still OPEN against the board staged in LDS.
+//                         election packets (LEADERs only, on both of hear_window's paths), then the timers, then
+//                         the claim evaluation of the tasks still OPEN against the board staged in LDS.
 // A receiver that is not LEADER at the start of the tick never handles a claim (hear() only ever leaves
-// FOLLOWER behind), so it ignores the claim bits and the claim cells: a claimer costs the followers around it
-// nothing.
-constexpr uint8_t kClaim = 4, kConflict = 8;
+// FOLLOWER behind), so it ignores the claim bits and the claim cells (hear_window's `rel` and `flag`): a
+// claimer costs the followers around it nothing.
 constexpr int kMaxTasks = 64;
 constexpr double kClaimThr = 20.0, kHysteresis = 5.0, kUScale = 100.0;
 // An OPEN task further than this (squared) is never claimed and never in the guard band: d2 > 25 gives
@@ -1061,25 +1068,6 @@ __global__ __launch_bounds__(kBlock) void k_task_sender_bytes(int64_t n2, const 
     for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n2; q += int64_t(gridDim.x) * kBlock)
         sb[q] = uint8_t((ob[q] & (kAcclaim | kHeartbeat)) | ((claim[q] & tmask) ? kClaim : 0) |
                         ((conflict[q] & tmask) ? kConflict : 0));
-}
-
-__global__ __launch_bounds__(kBlock) void k_radio_outbox_tasks(int64_t n, Radio w, TaskTick k) {
-    if (w.st[0] != 0) return;
-    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n; q += int64_t(gridDim.x) * kBlock) {
-        const uint8_t o = k.sb_in[w.sorted[q]];
-        const uint8_t fsm = o & (kAcclaim | kHeartbeat);
-        const bool cl = (o & kClaim) != 0, cf = (o & kConflict) != 0;
-        w.ob_sorted[q] = o;
-        if (o) {  // (every writer of a cell's byte stores the same 1)
-            const double2 p = w.psort[q];
-            const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
-            const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
-            const int64_t c = cy * w.g.ncx + cx;
-            if (fsm) w.cell_send[c] = 1;
-            if (cl) k.cell_claim[c] = 1;
-            if (cf) k.cell_conf[c] = 1;
-        }
-    }
 }
 
 // _handle_task_conflict (327-336) for every alive agent, over the conflict senders it hears, in ascending
@@ -1216,7 +1204,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
     }
     __syncthreads();
     const double now = double(t) * dt;
-    unsigned c_lead = 0, c_wait = 0, c_acc = 0, c_hb = 0, c_claim = 0, c_guard = 0;
+    TickCounts c;
+    unsigned c_claim = 0, c_guard = 0;
     ClaimRx cr{k.claim_in, pos, k.caps, nullptr, nullptr, s_tx, s_ty, s_rq, 0ull, 0u, 0u, k.tmask};
     // (the trip count is uniform over the workgroup: every wave enters wave_tasks with all its lanes)
     for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
@@ -1238,8 +1227,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
         }
         const int32_t me = ids[i];
         const uint8_t st0 = fw_state(fw);
-        const int32_t ph = fw_phase(fw);
-        const bool hb_tick = ((t + ph) % 10) == 0;
+        const bool hb_tick = ((t + fw_phase(fw)) % 10) == 0;
         uint32_t bits = fw_bits(fw);
         int32_t y = int32_t(r.y);
         Heard h{st0, 0, false, false, 0, -1};
@@ -1249,85 +1237,16 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
         cr.tw = k.tab_winner + i * k.T;
         cr.tu = k.tab_util + i * k.T;
         cr.conf = 0;
-        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
-        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
-        unsigned cells = 0;  // bit c: window cell c holds a sender this receiver listens to
-#pragma unroll
-        for (int c = 0; c < 9; ++c) {
-            const int64_t yy = cy + (c / 3) - 1, xx = cx + (c % 3) - 1;
-            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
-            const int64_t at = in ? yy * w.g.ncx + xx : 0;
-            uint8_t fl = w.cell_send[at];
-            if (lead0) fl |= k.cell_claim[at];
-            cells |= in && fl ? 1u << c : 0u;
-        }
-        const bool crowded = __popc(cells) > kHeardCells;
-        if (cells) {
-            int32_t sj[kHeardFast];
-            uint8_t so[kHeardFast];
-#pragma unroll
-            for (int u = 0; u < kHeardFast; ++u) {
-                sj[u] = kMergeEnd;
-                so[u] = 0;
-            }
-            bool more = crowded;
-            for (int c = 0; c < 9 && !crowded; ++c) {
-                if (!((cells >> c) & 1u)) continue;
-                const int64_t cell = (cy + (c / 3) - 1) * w.g.ncx + cx + (c % 3) - 1;
-                for (uint32_t q = w.off[cell], e = w.off[cell + 1]; q < e; ++q) {
-                    uint8_t o = w.ob_sorted[q] & rel;
-                    if (!o) continue;
-                    int32_t j = w.sorted[q];
-                    const double2 s = w.psort[q];
-                    const double ex = p.x - s.x, ey = p.y - s.y;
-                    if (j == int32_t(i) || !(ex * ex + ey * ey <= w.r2)) continue;
-#pragma unroll
-                    for (int u = 0; u < kHeardFast; ++u) {
-                        const bool lower = j < sj[u];
-                        const int32_t tj = sj[u];
-                        const uint8_t to = so[u];
-                        sj[u] = lower ? j : tj;
-                        so[u] = lower ? o : to;
-                        j = lower ? tj : j;
-                        o = lower ? to : o;
-                    }
-                    more |= j != kMergeEnd;  // an index fell off the end of the list
-                }
-            }
-            if (!more) {
-                int32_t ss[kHeardFast];  // the senders' IDs, all loads in flight
-#pragma unroll
-                for (int u = 0; u < kHeardFast; ++u) ss[u] = sj[u] != kMergeEnd ? ids[sj[u]] : 0;
-#pragma unroll
-                for (int u = 0; u < kHeardFast; ++u) {
-                    if (sj[u] == kMergeEnd) continue;
-                    hear(h, so[u], ss[u], sj[u], me, hb_tick);
-                    if ((so[u] & kClaim) && h.st == ST_L) hear_claims(cr, sj[u], ss[u]);
-                }
-            } else {
-                window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
-                    const uint8_t o = w.ob_sorted[q] & rel;
-                    if (!o || j == int32_t(i)) return;
-                    const double2 s = w.psort[q];
-                    const double ex = p.x - s.x, ey = p.y - s.y;
-                    if (!(ex * ex + ey * ey <= w.r2)) return;
-                    const int32_t sid = ids[j];
-                    hear(h, o, sid, j, me, hb_tick);
-                    if ((o & kClaim) && h.st == ST_L) hear_claims(cr, j, sid);
-                });
-            }
-        }
+        hear_window(
+            p, i, w, rel, ids,
+            [&](int64_t cell) { return uint8_t(w.cell_send[cell] | (lead0 ? k.cell_claim[cell] : uint8_t(0))); },
+            [&](uint8_t o, int32_t sid, int32_t j) {
+                hear(h, o, sid, j, me, hb_tick);
+                if ((o & kClaim) && h.st == ST_L) hear_claims(cr, j, sid);
+            });
         apply_heard(i, h, t, pos, f, bits, y);
-        const uint8_t ob = h.ob | timers(i, h.st, h.live, h.lead, h.lead_set, t, now, timeout, jitter, seed, ids,
-                                         ph, f, bits, y);
-        const uint32_t fw1 = fw_make(h.st, 1, bits, ph);
-        if (fw1 != fw || uint32_t(y) != r.y) f.rec[i] = make_uint2(fw1, uint32_t(y));
-        if (h.lead_set) f.lrec[i].leader = h.lead;
+        const uint8_t ob = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
         ob_out[i] = ob;
-        c_lead += h.st == ST_L;
-        c_wait += h.st == ST_W;
-        c_acc += (ob & kAcclaim) != 0;
-        c_hb += (ob & kHeartbeat) != 0;
         // _process_tasks (292-302): the tasks still OPEN after this tick's conflicts, at the tick's snapshot;
         // the status is read only when a task is near the wave at all
         unsigned long long claims = 0;
@@ -1336,13 +1255,13 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
             unsigned long long open = ~(lo | k.status_hi[i]) & reach;
             const uint32_t cp = k.caps[i];
             while (open) {
-                const int c = __ffsll((long long)open) - 1;
+                const int a = __ffsll((long long)open) - 1;
                 open &= open - 1;
-                const double dx = p.x - s_tx[c], dy = p.y - s_ty[c];
+                const double dx = p.x - s_tx[a], dy = p.y - s_ty[a];
                 if (!(dx * dx + dy * dy <= kClaimFar2)) continue;
-                const double U = utility(p.x, p.y, cp, s_tx[c], s_ty[c], s_rq[c], kUScale);
+                const double U = utility(p.x, p.y, cp, s_tx[a], s_ty[a], s_rq[a], kUScale);
                 c_guard += guard_flag(U, kClaimThr);
-                if (U > kClaimThr) claims |= 1ull << c;
+                if (U > kClaimThr) claims |= 1ull << a;
             }
             if (claims) k.status_lo[i] = lo | claims;  // TENTATIVE
         }
@@ -1352,7 +1271,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
         if (sent != old) k.sb_out[i] = sent;
         c_claim += unsigned(__popcll(claims));
     }
-    add_counts(c_lead, c_wait, c_acc, c_hb, s_cnt, counts);
+    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
     add_counts(c_claim, cr.handled, cr.sent, c_guard, s_tcnt, k.cnt);
 }
 
@@ -1539,7 +1458,8 @@ struct RadioState {
         rw.off = ls.off;
         rw.psort = ls.psort;
         SW_HIP(hipMemsetAsync(rw.cell_send, 0, cells, s));
-        hipLaunchKernelGGL(k_radio_outbox, grid, dim3(kBlock), 0, s, r.n, k.ob_in, rw);
+        hipLaunchKernelGGL(k_radio_outbox<false>, grid, dim3(kBlock), 0, s, r.n, k.ob_in, rw, (uint8_t *)nullptr,
+                           (uint8_t *)nullptr);
         SW_LAUNCHED();
         hipLaunchKernelGGL(k_tick_radio, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
                            r.timeout, r.jitter, r.seed, k.cnt);
@@ -1597,7 +1517,8 @@ struct TaskState {
                           sb + in,
                           sb + out};
         SW_HIP(hipMemsetAsync(rs.rw.cell_send, 0, 3 * rs.cells, s));
-        hipLaunchKernelGGL(k_radio_outbox_tasks, grid, dim3(kBlock), 0, s, r.n, rs.rw, tk);
+        hipLaunchKernelGGL(k_radio_outbox<true>, grid, dim3(kBlock), 0, s, r.n, tk.sb_in, rs.rw, tk.cell_claim,
+                           tk.cell_conf);
         SW_LAUNCHED();
         hipLaunchKernelGGL(k_task_conflicts, grid, dim3(kBlock), 0, s, r.n, r.ids, f.rec, rs.rw, tk);
         SW_LAUNCHED();

@@ -7,6 +7,10 @@
 // statements: their machine code is what S1's and U1-S's figures were measured on, and
 // window_separation through this function compiles k_physics_loop_sensed to 1 141 instructions for 1 169
 // (the candidate's position is loaded after the next head, not before).  New walkers go through this one.
+// window_cell is the window's "which of the nine cells are in the grid" for code that reads a per-cell array
+// (protocol.hip hear_window).  The merge below and protocol.hip k_task_conflicts keep the same arithmetic
+// written out: through window_cell, in any form tried, k_task_conflicts compiles to other instructions (757
+// against 708-915), and its machine code is what U1-T's figures were measured on.
 #pragma once
 
 #include "swarm_common.h"
@@ -14,6 +18,18 @@
 namespace swarm {
 
 constexpr int32_t kMergeEnd = 0x7fffffff;  // no head: the run is exhausted (n < 2^31 - 1)
+
+// Cell k (0 .. 8, row by row) of the 3 x 3 window around cell (cx, cy): whether it is in the grid, and its
+// index there (0 outside, so that a byte or an offset of it can be loaded ahead of the test).
+struct WindowCell {
+    bool in;
+    int64_t at;
+};
+__device__ __forceinline__ WindowCell window_cell(const Grid &g, int64_t cx, int64_t cy, int k) {
+    const int64_t yy = cy + (k / 3) - 1, xx = cx + (k % 3) - 1;
+    const bool in = yy >= 0 && yy < g.ncy && xx >= 0 && xx < g.ncx;
+    return {in, in ? yy * g.ncx + xx : 0};
+}
 
 template <class Visit>
 __device__ __forceinline__ void window_merge(double px, double py, const Grid &g,

@@ -546,6 +546,49 @@ def test_gpu_dense_block_of_claimers_and_leaders_over_all_nine_cells(oracle_mod)
     assert r["guard"] == want["guard"]
 
 
+@pytest.mark.gpu
+def test_gpu_follower_among_claimers_hears_its_one_heartbeat_and_the_leader_beside_it_the_claims(oracle_mod):
+    """What a receiver listens to decides which window cells and which sender bytes count for it.  FOLLOWER R
+    (index 12) and LEADER H (index 13, heartbeats at tick 1) share the middle cell of a 3 x 3 grid of side 2.5;
+    three claimers sit in each of the eight cells around them, all within Rc of both, each with a task of its
+    own 0.5 away.  At tick 2 R's window holds claimers in eight cells -- for a LEADER more than the sorted list
+    is tried for -- but the only sender R listens to is H: it takes the heartbeat and handles no claim.  H, in
+    the same crowd, handles all 24.  An anchor at the origin fixes the grid's corner."""
+    rc, n_cl = 2.5, 24
+    ring = [(dx, dy) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dx, dy) != (0, 0)]
+    jit = [(0.0, 0.0), (-0.2, 0.1), (0.15, -0.2)]
+    cl = [(3.75 + 1.55 * dx + jx, 3.75 + 1.55 * dy + jy) for dx, dy in ring for jx, jy in jit]
+    xy = cl[:12] + [(3.75, 3.75), (3.8, 3.75)] + cl[12:] + [(0.0, 0.0)]
+    ids = list(range(1, 13)) + [50, 99] + list(range(13, 25)) + [60]
+    bit = list(range(12)) + [None, None] + list(range(12, 24)) + [None]
+    caps = [0 if b is None else 1 << b for b in bit]
+    tasks = [(x, y + 0.5, b) for (x, y), b in zip(xy, bit) if b is not None]
+    n, R, H = len(ids), 12, 13
+    g = _hand(xy, ids, lead=(H,), caps=caps, tasks=tasks, off=[9 if i == H else 0 for i in range(n)], rc=rc)
+    s = _swarm(g, "input")
+    # the precondition, from the model's first tick: who claimed, who sent an election packet
+    one = _model(oracle_mod, s, g, 1)
+    claimed = one["claim_out"][1] != 0
+    sent = (np.asarray(one["fsm"]["outbox"])[n:] & 3) != 0
+    side = rc * (1.0 + 1e-9)  # the run's cells: max(Rc, min(Rs, 2)) widened by 1e-9, from the bounding box's corner
+    cx, cy = (np.minimum(np.floor((g[k] - g[k].min()) * (1.0 / side)), 2).astype(int) for k in ("x", "y"))
+    assert (cx[R], cy[R]) == (cx[H], cy[H]) == (1, 1) and claimed.sum() == n_cl
+    assert len({(a, b) for a, b in zip(cx[claimed], cy[claimed])}) >= 5  # (every cell of the grid is in R's window)
+    near = (g["x"] - g["x"][R]) ** 2 + (g["y"] - g["y"][R]) ** 2 <= rc * rc
+    near[R] = False
+    assert (near & claimed).sum() == n_cl and np.flatnonzero(near & sent).tolist() == [H]
+    want = _model(oracle_mod, s, g, 3)
+    np.testing.assert_array_equal(want["task_counts"], [[n_cl, 0, 0], [0, n_cl, n_cl], [0, 0, 0]])
+    r = _run(s, g, 3)
+    st = _state(s)
+    _assert_equal(st, want, ALL)
+    _assert_tasks(_task_state(s), want)
+    np.testing.assert_array_equal(r["task_counts"], want["task_counts"])
+    np.testing.assert_array_equal(r["counts"], want["counts"])
+    assert r["guard"] == want["guard"]
+    assert st["state"][R] == F and st["leader"][R] == 99 and st["state"][H] == L
+
+
 # 5. a large random swarm
 @pytest.mark.gpu
 def test_gpu_random_swarm_of_20001_agents_equals_the_model(oracle_mod):

@@ -9,12 +9,14 @@ legs taking turns run by run so that drift hits them alike):
   b  update_loop_tasks with every one of the 64 tasks out of everyone's reach: the per-agent task words are
      streamed, nothing is claimed;
   c  update_loop_radio: what a and b are reported against, in the same session;
-  d  update_loop_radio, update_loop_sensed, update_loop and protocol_run, whose kernels this loop leaves alone:
-     run it once on this tree and once with --pkg pointing at the parent commit's built package, under
-     different --label, in alternating processes, and compare.
+  d  update_loop_radio, update_loop_sensed, update_loop and protocol_run: the loops around this one
+     (update_loop_radio shares its window receive, all of them the agent's end of a tick);
+  e  protocol_run without a hearers graph (mode "pull": k_tick_pull, which no other leg runs).
+Against another commit: run it once on this tree and once with --pkg pointing at that commit's built package,
+under different --label, in alternating processes, and compare.
 Results are merged into --out under --label.
 
-Usage:  python tools/bench_loop_tasks.py [--agents N] [--legs a,b,c,d] [--label NAME] [--pkg DIR] [--out FILE]
+Usage:  python tools/bench_loop_tasks.py [--agents N] [--legs a,b,c,d,e] [--label NAME] [--pkg DIR] [--out FILE]
 """
 from __future__ import annotations
 
@@ -49,7 +51,7 @@ def main():
     from swarm_amd import _lib, gen
     from swarm_amd.swarm import Swarm
 
-    legs = [k for k in "abcd" if k in a.legs.split(",")]
+    legs = [k for k in "abcde" if k in a.legs.split(",")]
     dev = torch.device("cuda", 0)
     d = gen.swarm_inputs(a.agents, a.seed, deg=a.deg, t=1)
     sw = Swarm(d["ids"], d["x"], d["y"], d["caps"], device=dev).build_graph(1.0)
@@ -90,6 +92,7 @@ def main():
         "d_update_loop_sensed": lambda: sw.update_loop_sensed(ticks, rs, **kw),
         "d_update_loop": lambda: sw.update_loop(ticks, **kw),
         "d_protocol_run": lambda: sw.protocol_run(ticks, kill_ticks=kills, seed=5),
+        "e_protocol_run_pull": lambda: sw.protocol_run(ticks, kill_ticks=kills, seed=5, mode="pull"),
     }
     names = [k for k in runs if k[0] in legs]
     res = {"agents": n, "edges": e, "ticks": ticks, "kill_ticks": list(kills), "radio_radius": rc,
