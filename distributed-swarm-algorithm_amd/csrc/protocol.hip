@@ -54,6 +54,7 @@
 #include <cstring>
 
 #include "fsm_records.h"
+#include "link_loss.h"
 #include "tick_segments.h"
 #include "utility.h"
 #include "window_merge.h"
@@ -976,6 +977,17 @@ __device__ __forceinline__ void hear_window(double2 p, int64_t i, const Radio &w
     }
 }
 
+// The channel of a lossy tick (contract U1-L; link_loss.h): the link j -> i is dropped at tick t iff
+// link_dropped(seed, t, ids[j], ids[i], loss), and a dropped link delivers nothing of j's tick t-1 sends.  cnt:
+// the tick's kShards x 4 link counters -- [0] the election links (alive receiver, in-range sender with an
+// ACCLAIM or a HEARTBEAT), [1] those of them that were dropped.  The lossy kernels are siblings of the
+// plain ones, which keep their instructions.
+struct Lossy {
+    double loss;
+    uint64_t seed;
+    unsigned long long *cnt;
+};
+
 // k_tick_pull's agent over the window: threads in cell-sorted order (a wave's lanes share their windows and
 // the nine sender bytes; the records are gathered by storage index), the row walk replaced by hear_window.
 // Returns at once when a tick of the call was refused (the caller restores every array).
@@ -1010,6 +1022,49 @@ __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, con
         ob_out[i] = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
     }
     add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
+}
+
+// k_tick_radio over a lossy channel: hear_window's `sender` judges the link first, counts it, and returns when
+// it is dropped.  (A copy of k_tick_radio's text, not one template for both: with the two folded into one body
+// the plain kernel came out with another register allocation, and it has to keep its instructions.)
+__global__ __launch_bounds__(kBlock) void k_tick_radio_lossy(int64_t n, int64_t t, const int32_t *__restrict__ ids,
+                                                            const double2 *__restrict__ pos, Fsm f, Radio w,
+                                                            uint8_t *__restrict__ ob_out, double dt, double timeout,
+                                                            double jitter, uint64_t seed,
+                                                            unsigned long long *__restrict__ counts, Lossy ch) {
+    __shared__ unsigned s_cnt[4], s_lcnt[4];
+    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = s_lcnt[threadIdx.x] = 0;
+    __syncthreads();
+    const double now = double(t) * dt;
+    TickCounts c;
+    unsigned links = 0, lost = 0;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const int64_t i = w.sorted[q0];
+        const uint2 r = f.rec[i];
+        if (!fw_alive(r.x)) {
+            ob_out[i] = 0;
+            continue;
+        }
+        const double2 p = w.psort[q0];
+        const int32_t me = ids[i];
+        const bool hb_tick = ((t + fw_phase(r.x)) % 10) == 0;
+        uint32_t bits = fw_bits(r.x);
+        int32_t y = int32_t(r.y);
+        Heard h{fw_state(r.x), 0, false, false, 0, -1};
+        // (0xFF, not the two outbox bits: the pass wrote the byte masked, the `&` folds away)
+        hear_window(p, i, w, 0xFF, ids, [&](int64_t cell) { return w.cell_send[cell]; },
+                    [&](uint8_t o, int32_t sid, int32_t j) {
+                        const bool drop = link_dropped(ch.seed, t, sid, me, ch.loss);
+                        ++links;  // every sender of this window sent an election packet
+                        lost += drop;
+                        if (!drop) hear(h, o, sid, j, me, hb_tick);
+                    });
+        apply_heard(i, h, t, pos, f, bits, y);
+        ob_out[i] = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
+    }
+    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
+    add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
 }
 
 // ---------------------------------------------------------------- task update loop (contract U1-T)
@@ -1106,6 +1161,53 @@ __global__ __launch_bounds__(kBlock) void k_task_conflicts(int64_t n, const int3
                 const unsigned long long bit = 1ull << t;
                 hi |= bit;  // ASSIGNED (3) for the winner, LOCKED (2) for everyone else
                 lo = row[t] == me ? lo | bit : lo & ~bit;
+            }
+        });
+        if (lo != lo0) k.status_lo[i] = lo;
+        if (hi != hi0) k.status_hi[i] = hi;
+    }
+}
+
+// k_task_conflicts over a lossy channel: a conflict sender in range is heard only over a link that tick t
+// keeps -- the verdict the tick kernel reaches for the same (t, sender, receiver); the sender's ID is gathered
+// for that alone.  (A copy, as k_tick_radio_lossy.)
+__global__ __launch_bounds__(kBlock) void k_task_conflicts_lossy(int64_t n, int64_t t,
+                                                                const int32_t *__restrict__ ids,
+                                                                const uint2 *__restrict__ rec, Radio w, TaskTick k,
+                                                                Lossy ch) {
+    if (w.st[0] != 0) return;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const double2 p = w.psort[q0];
+        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+        uint8_t any = 0;  // the nine bytes loaded at once
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const int64_t yy = cy + (c / 3) - 1, xx = cx + (c % 3) - 1;
+            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
+            const uint8_t fl = k.cell_conf[in ? yy * w.g.ncx + xx : 0];
+            any |= in ? fl : uint8_t(0);
+        }
+        if (!any) continue;
+        const int64_t i = w.sorted[q0];
+        if (!fw_alive(rec[i].x)) continue;
+        const int32_t me = ids[i];
+        const unsigned long long lo0 = k.status_lo[i], hi0 = k.status_hi[i];
+        unsigned long long lo = lo0, hi = hi0;
+        window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
+            if (!(w.ob_sorted[q] & kConflict) || j == int32_t(i)) return;
+            const double2 s = w.psort[q];
+            const double ex = p.x - s.x, ey = p.y - s.y;
+            if (!(ex * ex + ey * ey <= w.r2)) return;
+            if (link_dropped(ch.seed, t, ids[j], me, ch.loss)) return;
+            unsigned long long m = k.conflict_in[j] & k.tmask;
+            const int32_t *row = k.tab_winner + int64_t(j) * k.T;
+            while (m) {
+                const int a = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const unsigned long long bit = 1ull << a;
+                hi |= bit;  // ASSIGNED (3) for the winner, LOCKED (2) for everyone else
+                lo = row[a] == me ? lo | bit : lo & ~bit;
             }
         });
         if (lo != lo0) k.status_lo[i] = lo;
@@ -1275,6 +1377,103 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
     add_counts(c_claim, cr.handled, cr.sent, c_guard, s_tcnt, k.cnt);
 }
 
+// k_tick_radio_tasks over a lossy channel: the link is judged before the sender's election packets and claims
+// are handled.  (A copy, as k_tick_radio_lossy.)
+__global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks_lossy(
+    int64_t n, int64_t t, const int32_t *__restrict__ ids, const double2 *__restrict__ pos, Fsm f, Radio w,
+    uint8_t *__restrict__ ob_out, double dt, double timeout, double jitter, uint64_t seed,
+    unsigned long long *__restrict__ counts, TaskTick k, Lossy ch) {
+    __shared__ unsigned s_cnt[4], s_tcnt[4], s_lcnt[4];
+    __shared__ double s_tx[kMaxTasks], s_ty[kMaxTasks];
+    __shared__ int8_t s_rq[kMaxTasks];
+    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = s_tcnt[threadIdx.x] = s_lcnt[threadIdx.x] = 0;
+    if (int(threadIdx.x) < k.T) {
+        const double2 q = k.tpos[threadIdx.x];
+        s_tx[threadIdx.x] = q.x;
+        s_ty[threadIdx.x] = q.y;
+        s_rq[threadIdx.x] = k.treq[threadIdx.x];
+    }
+    __syncthreads();
+    const double now = double(t) * dt;
+    TickCounts c;
+    unsigned c_claim = 0, c_guard = 0, links = 0, lost = 0;
+    ClaimRx cr{k.claim_in, pos, k.caps, nullptr, nullptr, s_tx, s_ty, s_rq, 0ull, 0u, 0u, k.tmask};
+    // (the trip count is uniform over the workgroup: every wave enters wave_tasks with all its lanes)
+    for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
+        const int64_t q0 = base + threadIdx.x;
+        const bool valid = q0 < n;
+        const double2 p = valid ? w.psort[q0] : make_double2(kNaN, kNaN);
+        const unsigned long long reach = wave_tasks(p, k.T, s_tx, s_ty);
+        if (!valid) continue;
+        const int64_t i = w.sorted[q0];
+        const uint2 r = f.rec[i];
+        const uint32_t fw = r.x;
+        const uint8_t old = k.sb_out[i];  // what this slot's words hold (tick t-2's sends)
+        if (!fw_alive(fw)) {
+            ob_out[i] = 0;
+            if (old & kClaim) k.claim_out[i] = 0;
+            if (old & kConflict) k.conflict_out[i] = 0;
+            if (old) k.sb_out[i] = 0;
+            continue;
+        }
+        const int32_t me = ids[i];
+        const uint8_t st0 = fw_state(fw);
+        const bool hb_tick = ((t + fw_phase(fw)) % 10) == 0;
+        uint32_t bits = fw_bits(fw);
+        int32_t y = int32_t(r.y);
+        Heard h{st0, 0, false, false, 0, -1};
+        // only a LEADER's walk looks at claims (see the header)
+        const bool lead0 = st0 == ST_L;
+        const uint8_t rel = uint8_t(kAcclaim | kHeartbeat | (lead0 ? kClaim : 0));
+        cr.tw = k.tab_winner + i * k.T;
+        cr.tu = k.tab_util + i * k.T;
+        cr.conf = 0;
+        hear_window(
+            p, i, w, rel, ids,
+            [&](int64_t cell) { return uint8_t(w.cell_send[cell] | (lead0 ? k.cell_claim[cell] : uint8_t(0))); },
+            [&](uint8_t o, int32_t sid, int32_t j) {
+                // (a claim-only sender is no election link; it is dropped all the same)
+                const bool drop = link_dropped(ch.seed, t, sid, me, ch.loss);
+                const unsigned el = (o & (kAcclaim | kHeartbeat)) != 0;
+                links += el;
+                lost += el & unsigned(drop);
+                if (drop) return;
+                hear(h, o, sid, j, me, hb_tick);
+                if ((o & kClaim) && h.st == ST_L) hear_claims(cr, j, sid);
+            });
+        apply_heard(i, h, t, pos, f, bits, y);
+        const uint8_t ob = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
+        ob_out[i] = ob;
+        // _process_tasks (292-302): the tasks still OPEN after this tick's conflicts, at the tick's snapshot;
+        // the status is read only when a task is near the wave at all
+        unsigned long long claims = 0;
+        if (reach) {
+            const unsigned long long lo = k.status_lo[i];
+            unsigned long long open = ~(lo | k.status_hi[i]) & reach;
+            const uint32_t cp = k.caps[i];
+            while (open) {
+                const int a = __ffsll((long long)open) - 1;
+                open &= open - 1;
+                const double dx = p.x - s_tx[a], dy = p.y - s_ty[a];
+                if (!(dx * dx + dy * dy <= kClaimFar2)) continue;
+                const double U = utility(p.x, p.y, cp, s_tx[a], s_ty[a], s_rq[a], kUScale);
+                c_guard += guard_flag(U, kClaimThr);
+                if (U > kClaimThr) claims |= 1ull << a;
+            }
+            if (claims) k.status_lo[i] = lo | claims;  // TENTATIVE
+        }
+        if (claims || (old & kClaim)) k.claim_out[i] = claims;
+        if (cr.conf || (old & kConflict)) k.conflict_out[i] = cr.conf;
+        const uint8_t sent = uint8_t(ob | (claims ? kClaim : 0) | (cr.conf ? kConflict : 0));
+        if (sent != old) k.sb_out[i] = sent;
+        c_claim += unsigned(__popcll(claims));
+    }
+    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
+    add_counts(c_claim, cr.handled, cr.sent, c_guard, s_tcnt, k.cnt);
+    add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
+}
+
 // ---------------------------------------------------------------- the host loop, in stages
 // One run's arguments, as the five entry points fill them (`loop`: swarm_update_loop*, each tick then followed
 // by its physics step; `pos` is not used then, the heartbeats read the lagged buffer).
@@ -1297,7 +1496,10 @@ struct TickRun {
     void *stream;
     const swarm_tasks *tasks = nullptr;  // U1-T (T > 0: swarm_update_loop_tasks), with its two host outputs
     int64_t *task_counts = nullptr, *n_guard = nullptr;
+    const swarm_channel *ch = nullptr;  // U1-L (loss > 0: swarm_update_loop_channel's lossy kernels)
+    int64_t *link_counts = nullptr;
     bool tasked() const { return tasks && tasks->T > 0; }
+    bool lossy() const { return ch && ch->loss > 0.0; }
     bool sensed() const { return loop && loop->sense_radius > 0.0; }
     bool radio() const { return loop && loop->radio_radius > 0.0; }
     bool push() const { return hear_row_ptr != nullptr; }
@@ -1452,7 +1654,8 @@ struct RadioState {
         return SWARM_OK;
     }
 
-    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, hipStream_t s) {
+    // ch: the tick's channel on a lossy run (LinkState::of), else NULL
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, const Lossy *ch, hipStream_t s) {
         const dim3 grid(grid_for(r.n, kBlock, 8192));
         rw.sorted = ls.sorted;
         rw.off = ls.off;
@@ -1461,10 +1664,31 @@ struct RadioState {
         hipLaunchKernelGGL(k_radio_outbox<false>, grid, dim3(kBlock), 0, s, r.n, k.ob_in, rw, (uint8_t *)nullptr,
                            (uint8_t *)nullptr);
         SW_LAUNCHED();
-        hipLaunchKernelGGL(k_tick_radio, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
-                           r.timeout, r.jitter, r.seed, k.cnt);
+        if (ch)
+            hipLaunchKernelGGL(k_tick_radio_lossy, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out,
+                               r.dt, r.timeout, r.jitter, r.seed, k.cnt, *ch);
+        else
+            hipLaunchKernelGGL(k_tick_radio, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
+                               r.timeout, r.jitter, r.seed, k.cnt);
         SW_LAUNCHED();
         return SWARM_OK;
+    }
+};
+
+// A lossy run (U1-L): the per-tick link counters, sharded and summed as the tick counts.
+struct LinkState {
+    unsigned long long *part = nullptr, *sums = nullptr;
+
+    int begin(const TickRun &r, hipStream_t s) {
+        const size_t ticks = size_t(r.ticks), part_bytes = ticks * kShards * 4 * 8;
+        SW_ALLOC(part, r.ctx, S_LINK_COUNTS, part_bytes + ticks * 4 * 8);
+        sums = part + ticks * kShards * 4;
+        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
+        return SWARM_OK;
+    }
+
+    Lossy of(const TickRun &r, int64_t t) const {
+        return Lossy{r.ch->loss, r.ch->seed, part + size_t(t - r.t0 - 1) * kShards * 4};
     }
 };
 
@@ -1490,7 +1714,8 @@ struct TaskState {
         return SWARM_OK;
     }
 
-    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, RadioState &rs, hipStream_t s) {
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, RadioState &rs, const Lossy *ch,
+               hipStream_t s) {
         const dim3 grid(grid_for(r.n, kBlock, 8192));
         const swarm_tasks &b = *r.tasks;
         const size_t un = size_t(r.n), in = size_t((k.t - 1) & 1) * un, out = size_t(k.t & 1) * un;
@@ -1520,10 +1745,18 @@ struct TaskState {
         hipLaunchKernelGGL(k_radio_outbox<true>, grid, dim3(kBlock), 0, s, r.n, tk.sb_in, rs.rw, tk.cell_claim,
                            tk.cell_conf);
         SW_LAUNCHED();
-        hipLaunchKernelGGL(k_task_conflicts, grid, dim3(kBlock), 0, s, r.n, r.ids, f.rec, rs.rw, tk);
+        if (ch)
+            hipLaunchKernelGGL(k_task_conflicts_lossy, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec, rs.rw, tk,
+                               *ch);
+        else
+            hipLaunchKernelGGL(k_task_conflicts, grid, dim3(kBlock), 0, s, r.n, r.ids, f.rec, rs.rw, tk);
         SW_LAUNCHED();
-        hipLaunchKernelGGL(k_tick_radio_tasks, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw, k.ob_out,
-                           r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk);
+        if (ch)
+            hipLaunchKernelGGL(k_tick_radio_tasks_lossy, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
+                               k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk, *ch);
+        else
+            hipLaunchKernelGGL(k_tick_radio_tasks, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
+                               k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk);
         SW_LAUNCHED();
         return SWARM_OK;
     }
@@ -1656,21 +1889,30 @@ int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t,
 // run's one final host wait (none when nothing is asked for).  A refused tick (`snap` restores the caller's
 // arrays) withholds the counts and the singular count and sets refused_tick.
 int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap,
-              const TaskState &ts, hipStream_t s) {
+              const TaskState &ts, const LinkState &lk, hipStream_t s) {
     const bool want_sing = r.loop && r.loop->n_singular;
     const bool want_tasks = r.tasked() && (r.task_counts || r.n_guard);
+    const bool want_links = r.lossy() && r.link_counts;
     if (r.traffic) {  // (pull-mode runs: every tick walks every row -- the receivers are all agents)
         hipLaunchKernelGGL(k_sum_traffic, dim3(1), dim3(kWave), 0, s, c.tr_shards, c.tr_sums);
         SW_LAUNCHED();
     }
     if (ls)
         if (const int rc = snap.restore_if_refused(ls->st, s)) return rc;
-    if (!(r.traffic || ls || want_sing || r.counts || want_tasks)) return SWARM_OK;
+    if (!(r.traffic || ls || want_sing || r.counts || want_tasks || want_links)) return SWARM_OK;
     const size_t cnt_bytes = r.counts ? size_t(r.ticks) * 4 * 8 : 0;
     const size_t tcnt_bytes = want_tasks ? size_t(r.ticks) * 4 * 8 : 0;  // after the counts
-    unsigned long long *h = static_cast<unsigned long long *>(pinned(r.ctx, 128 + cnt_bytes + tcnt_bytes));
+    const size_t lcnt_bytes = want_links ? size_t(r.ticks) * 4 * 8 : 0;  // after the task counts
+    unsigned long long *h =
+        static_cast<unsigned long long *>(pinned(r.ctx, 128 + cnt_bytes + tcnt_bytes + lcnt_bytes));
     if (!h) return SWARM_ERR_OOM;
-    unsigned long long *ht = h + 16 + cnt_bytes / 8;
+    unsigned long long *ht = h + 16 + cnt_bytes / 8, *hl = ht + tcnt_bytes / 8;
+    if (want_links) {
+        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
+                           int64_t(r.ticks), lk.part, lk.sums);
+        SW_LAUNCHED();
+        SW_HIP(hipMemcpyAsync(hl, lk.sums, lcnt_bytes, hipMemcpyDeviceToHost, s));
+    }
     if (want_tasks) {
         hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
                            int64_t(r.ticks), ts.part, ts.sums);
@@ -1704,6 +1946,9 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
         }
         if (r.n_guard) *r.n_guard = guard;
     }
+    if (want_links)
+        for (int64_t q = 0; q < r.ticks; ++q)
+            for (int c = 0; c < 2; ++c) r.link_counts[2 * q + c] = int64_t(hl[4 * q + c]);
     return SWARM_OK;
 }
 
@@ -1714,6 +1959,7 @@ int run_ticks(const TickRun &r) {
     if (r.traffic) for (int q = 0; q < kTraffic; ++q) r.traffic[q] = 0;
     if (r.task_counts) for (int64_t q = 0; q < int64_t(r.ticks) * 3; ++q) r.task_counts[q] = 0;
     if (r.n_guard) *r.n_guard = 0;
+    if (r.lossy() && r.link_counts) for (int64_t q = 0; q < int64_t(r.ticks) * 2; ++q) r.link_counts[q] = 0;
     if (r.n == 0 || r.ticks == 0) {
         if (r.counts) for (int64_t q = 0; q < int64_t(r.ticks) * 4; ++q) r.counts[q] = 0;
         return SWARM_OK;
@@ -1740,11 +1986,14 @@ int run_ticks(const TickRun &r) {
     PushState ps;
     RadioState rs;
     TaskState ts;
+    LinkState lk;
     TickClocks clk;
     if (push && (rc = ps.begin(r, grid, s))) return rc;
     if ((rc = clk.begin(r, ps, s))) return rc;
     if (radio && (rc = rs.begin(r, ls, tasked ? 3 : 1))) return rc;
     if (tasked && (rc = ts.begin(r, s))) return rc;
+    const bool lossy = radio && r.lossy();
+    if (lossy && (rc = lk.begin(r, s))) return rc;
     double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
     for (int64_t t = r.t0 + 1; t <= r.t0 + r.ticks; ++t) {
         // (a heartbeat sent during tick t-1 carries its sender's position of then: the loops' lagged buffer)
@@ -1758,8 +2007,9 @@ int run_ticks(const TickRun &r) {
         // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell (the call's grid reaches
         // far beyond the agents: offsets by search)
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
-        rc = tasked ? ts.launch(r, f, k, ls, rs, s)
-             : radio  ? rs.launch(r, f, k, ls, s)
+        const Lossy ch = lossy ? lk.of(r, t) : Lossy{};
+        rc = tasked ? ts.launch(r, f, k, ls, rs, lossy ? &ch : nullptr, s)
+             : radio  ? rs.launch(r, f, k, ls, lossy ? &ch : nullptr, s)
              : push ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
                     : launch_tick_pull(r, grid, f, k, s);
         if (rc) return rc;
@@ -1774,7 +2024,7 @@ int run_ticks(const TickRun &r) {
     hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, r.fsm->state, r.fsm->alive,
                        r.fsm->has_leader_pos, r.fsm->leader, reinterpret_cast<float2 *>(r.fsm->leader_pos), f);
     SW_LAUNCHED();
-    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts, s);
+    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts, lk, s);
 }
 
 // The three loop entry points' own arguments (run_ticks checks the rest): U1 takes a sensor CSR and n < 2^31,
@@ -1824,6 +2074,12 @@ int check_tasks(swarm_ctx *ctx, int64_t n, const swarm_tasks *b, void *stream) {
     SW_HIP(hipMemcpyAsync(rq, b->treq, size_t(b->T), hipMemcpyDeviceToHost, s));
     SW_HIP(hipStreamSynchronize(s));
     for (int k = 0; k < b->T; ++k) SW_ARG(!bad_req(rq[k]), "a treq outside [-1, 31]");
+    return SWARM_OK;
+}
+
+// swarm_update_loop_channel's own argument (NULL: the ideal channel).
+int check_channel(const swarm_channel *ch) {
+    SW_ARG(ch == nullptr || (ch->loss >= 0.0 && ch->loss <= 1.0), "loss must be in [0, 1]");
     return SWARM_OK;
 }
 
@@ -1921,6 +2177,34 @@ int swarm_update_loop_tasks(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
     r.task_counts = task_counts;
     r.n_guard = n_guard;
     return run_loop(kLoopRadio, r);
+}
+
+int swarm_update_loop_channel(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                              const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                              double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                              int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                              const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                              double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                              int64_t *refused_tick, const swarm_tasks *tasks, int64_t *task_counts,
+                              int64_t *n_guard, void *stream, const swarm_channel *ch, int64_t *link_counts) {
+    using namespace swarm;
+    if (const int rc = check_channel(ch)) return rc;
+    if (tasks)
+        if (const int rc = check_tasks(ctx, n, tasks, stream)) return rc;
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
+                        trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
+    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream};
+    r.tasks = tasks;
+    r.task_counts = task_counts;
+    r.n_guard = n_guard;
+    r.ch = ch;
+    r.link_counts = link_counts;
+    return run_loop(kLoopRadio, r);
+}
+
+int swarm_link_dropped(uint64_t seed, int64_t t, int32_t sid, int32_t rid, double loss) {
+    return swarm::link_dropped(seed, t, sid, rid, loss) ? 1 : 0;
 }
 
 }  // extern "C"

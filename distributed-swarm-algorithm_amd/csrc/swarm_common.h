@@ -66,6 +66,7 @@ enum Slot {
     S_RADIO_CELLS,    // radio update loop: one byte per grid cell, set when the cell holds a sender
     S_TASK_COUNTS,    // task update loop: the per-tick task counters (sharded) and their sums
     S_TASK_SENDERS,   // task update loop: one byte per agent and tick parity, what it sent (outbox + task bits)
+    S_LINK_COUNTS,    // lossy update loops: the per-tick link counters (sharded) and their sums
     S_NUM
 };
 

@@ -40,7 +40,7 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_frontier_set_compact_escaped", "swarm_physics_run_sensed", "swarm_update_loop",
            "swarm_update_loop_sensed", "swarm_update_loop_radio", "swarm_update_loop_tasks",
            "swarm_obstacle_field_create", "swarm_obstacle_field_obstacles", "swarm_obstacle_field_read",
-           "swarm_obstacle_field_destroy")
+           "swarm_obstacle_field_destroy", "swarm_update_loop_channel", "swarm_link_dropped")
 
 
 class SwarmError(RuntimeError):
@@ -59,6 +59,11 @@ class Tasks(ctypes.Structure):
     _fields_ = [("T", ctypes.c_int32)] + \
                [(k, ctypes.c_void_p) for k in ("tpos", "treq", "caps", "status_lo", "status_hi", "claim_out",
                                                "conflict_out", "tab_winner", "tab_util")]
+
+
+class Channel(ctypes.Structure):
+    """swarm_channel: the lossy channel of swarm_update_loop_channel."""
+    _fields_ = [("loss", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
 class ObstacleFieldInfo(ctypes.Structure):
@@ -194,6 +199,8 @@ def load(path: str = LIB_PATH):
                                               ctypes.POINTER(i64), ctypes.POINTER(i64), P]
         L.swarm_update_loop_tasks.argtypes = L.swarm_update_loop_radio.argtypes[:-1] + [
             ctypes.POINTER(Tasks), P, ctypes.POINTER(i64), P]
+        L.swarm_update_loop_channel.argtypes = L.swarm_update_loop_tasks.argtypes + [ctypes.POINTER(Channel), P]
+        L.swarm_link_dropped.argtypes = [ctypes.c_uint64, i64, i32, i32, d]
         L.swarm_auction_begin.argtypes = [P, i64, P, P, P, i64, P, P, d, d, ctypes.c_float, P, P, P, P, P]
         L.swarm_auction_bid.argtypes = [P, i64, i32, i32, P, P, P, P]
         L.swarm_auction_resolve.argtypes = [P, i64, i32, P, P, P, P, P, P]

@@ -188,6 +188,15 @@ class ObstacleField:
         return self.m, self._ptr
 
 
+def _channel(loss, loss_seed):
+    """The radio loops' loss keywords -> (loss, seed) for swarm_update_loop_channel, or None for the ideal
+    channel (the loss-free entry points, exactly as without the keywords)."""
+    loss = float(loss)
+    if not 0.0 <= loss <= 1.0:  # (NaN fails both comparisons)
+        raise ValueError(f"loss must be in [0, 1], got {loss}")
+    return (loss, int(loss_seed) & 0xFFFFFFFFFFFFFFFF) if loss > 0.0 else None
+
+
 def _obstacle_args(obstacles, dev):
     """(m, pointer or None, keep-alive) of an `obstacles=` argument: a list or an ObstacleField."""
     if isinstance(obstacles, ObstacleField):
@@ -866,7 +875,8 @@ class Swarm:
 
     def update_loop_radio(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
                           kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
-                          max_speed: float = 5.0, trace_every: int = 0) -> dict:
+                          max_speed: float = 5.0, trace_every: int = 0, loss: float = 0.0,
+                          loss_seed: int = 0) -> dict:
         """update_loop_sensed with who hears whom re-sensed every tick as well (contract U1-R;
         swarm_update_loop_radio): at tick t an alive agent hears every other agent within radio_radius of it in
         the positions at the start of the tick -- the snapshot the tick's sensors read -- and receives what
@@ -877,13 +887,22 @@ class Swarm:
         with no graph built: the swarm needs no neighbour graph, and self.row_ptr / self.col are untouched
         when it has one.  Keywords, self.fsm / self.fsm_tick / self.pos_prev, the returned dict, the
         all-or-nothing refusal of a too-dense tick and self.last_refused_tick as update_loop_sensed; the calls
-        of the three loops chain into one run."""
+        of the three loops chain into one run.
+        loss > 0: a lossy channel (contract U1-L; swarm_update_loop_channel).  At absolute tick t the link
+        from an in-range sender to a receiver is dropped with probability `loss`, decided by a hash of
+        (loss_seed, t, sender ID, receiver ID) -- the same in every layout and however the run is cut into
+        calls -- and a dropped link delivers nothing of what the sender sent during tick t-1.  The two
+        directions of a pair are decided independently.  The dict then gains "link_counts" (ticks x 2): per
+        tick the election links (alive receiver, in-range sender with an ACCLAIM or a HEARTBEAT) and how many
+        of them were dropped.  loss outside [0, 1] or NaN raises ValueError; with the default 0.0 the call is
+        the loss-free one, whatever loss_seed is."""
         radio_radius, sense_radius = float(radio_radius), float(sense_radius)
         for name, r in (("radio_radius", radio_radius), ("sense_radius", sense_radius)):
             if not (r > 0.0 and np.isfinite(r)):
                 raise ValueError(f"{name} must be positive and finite, got {r}")
         return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
-                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius)
+                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius,
+                                 channel=_channel(loss, loss_seed))
 
     # ------------------------------------------------------------------ task update loop (U1-T)
     def set_tasks(self, tx, ty=None, treq=None):
@@ -917,7 +936,8 @@ class Swarm:
 
     def update_loop_tasks(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
                           kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
-                          max_speed: float = 5.0, trace_every: int = 0) -> dict:
+                          max_speed: float = 5.0, trace_every: int = 0, loss: float = 0.0,
+                          loss_seed: int = 0) -> dict:
         """update_loop_radio with the reference's task logic run every tick on the board of set_tasks
         (contract U1-T; swarm_update_loop_tasks; agent.py:292-336): an agent claims a task on the tick it is
         within reach of it (U > 20 at the tick's snapshot) and marks it TENTATIVE; only a LEADER that hears
@@ -928,7 +948,10 @@ class Swarm:
         chaining with the other three loops as update_loop_radio; claims and conflicts in flight carry over
         between calls.  Returns update_loop_radio's dict plus "task_counts" (ticks x 3: TASK_CLAIMs sent,
         claims handled by a LEADER, TASK_CONFLICT messages sent) and "guard", the evaluated (agent, task)
-        pairs whose utility is so close to 20 that libm pow arithmetic could have decided differently."""
+        pairs whose utility is so close to 20 that libm pow arithmetic could have decided differently.
+        loss / loss_seed: update_loop_radio's lossy channel; a dropped link delivers neither the sender's
+        election packets nor its TASK_CLAIMs nor its TASK_CONFLICTs, and "link_counts" is returned as there."""
+        channel = _channel(loss, loss_seed)
         if not hasattr(self, "tasks"):
             raise RuntimeError("no task board: call set_tasks() first")
         radio_radius, sense_radius = float(radio_radius), float(sense_radius)
@@ -936,7 +959,8 @@ class Swarm:
             if not (r > 0.0 and np.isfinite(r)):
                 raise ValueError(f"{name} must be positive and finite, got {r}")
         return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
-                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius, tasks=self.tasks)
+                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius, tasks=self.tasks,
+                                 channel=channel)
 
     def task_status(self) -> torch.Tensor:
         """(n, T) uint8 status codes (indices into STATUS_NAMES), storage order."""
@@ -966,9 +990,10 @@ class Swarm:
                              for k, tid in enumerate(task_ids) if w[i, k] >= 0}
 
     def _update_loop(self, ticks, sense_radius, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed,
-                     max_speed, mode, pull_frac, trace_every, radio_radius=None, tasks=None) -> dict:
+                     max_speed, mode, pull_frac, trace_every, radio_radius=None, tasks=None, channel=None) -> dict:
         """update_loop (sense_radius None: the `sensors` lists, fixed), update_loop_sensed,
-        update_loop_radio (radio_radius given: no message graph) and update_loop_tasks (tasks: the board)."""
+        update_loop_radio (radio_radius given: no message graph) and update_loop_tasks (tasks: the board);
+        channel: (loss, loss_seed) with loss > 0 -- the two radio loops through swarm_update_loop_channel."""
         ticks, trace_every = int(ticks), int(trace_every)
         if mode not in ("push", "pull", "hybrid"):
             raise ValueError(f"unknown mode {mode!r}")
@@ -1016,6 +1041,7 @@ class Swarm:
                     *(() if radio_radius is not None else (float(pull_frac) if mode == "hybrid" else -1.0,)), *motion)
             tail = (float(max_speed), _lib.ptr(trace) if frames and n else None, trace_every,
                     counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(sing))
+            tk, task_counts, guard = None, None, ctypes.c_int64(0)
             if tasks is not None:
                 T = tasks["T"]
                 if any(tasks[k].shape[0] != size for k, size in (("status_lo", n), ("claim_out", 2 * n))):
@@ -1025,7 +1051,16 @@ class Swarm:
                                 *[tp(k) for k in ("status_lo", "status_hi", "claim_out", "conflict_out",
                                                   "tab_winner", "tab_util")])
                 task_counts = np.zeros((ticks, 3), np.int64)
-                guard = ctypes.c_int64(0)
+            if channel is not None:
+                ch = _lib.Channel(channel[0], channel[1])
+                link_counts = np.zeros((ticks, 2), np.int64)
+                rc = _lib.lib().swarm_update_loop_channel(
+                    *head, float(radio_radius), float(sense_radius), *tail, ctypes.byref(refused),
+                    ctypes.byref(tk) if tk is not None else None,
+                    task_counts.ctypes.data_as(ctypes.c_void_p) if tk is not None else None, ctypes.byref(guard),
+                    _lib.stream(), ctypes.byref(ch), link_counts.ctypes.data_as(ctypes.c_void_p))
+                self.last_refused_tick = refused.value
+            elif tasks is not None:
                 rc = _lib.lib().swarm_update_loop_tasks(*head, float(radio_radius), float(sense_radius), *tail,
                                                         ctypes.byref(refused), ctypes.byref(tk),
                                                         task_counts.ctypes.data_as(ctypes.c_void_p),
@@ -1053,6 +1088,8 @@ class Swarm:
             out["trace"] = trace
         if tasks is not None:
             out["task_counts"], out["guard"] = task_counts, guard.value
+        if channel is not None:
+            out["link_counts"] = link_counts
         return out
 
     # ------------------------------------------------------------------ views / bridge

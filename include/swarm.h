@@ -747,6 +747,49 @@ int swarm_update_loop_tasks(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             int64_t *n_guard, void *stream);
 
 /*
+ * swarm_update_loop_radio / swarm_update_loop_tasks over a lossy channel (contract U1-L).  Inside
+ * radio_radius the ideal channel delivers every packet; here, at absolute tick t (t0 + 1 .. t0 + ticks), the
+ * link from in-range sender j (ID sid) to alive receiver i (ID rid), j != i, is dropped iff
+ *     u(ch->seed, t, sid, rid) < ch->loss,
+ * and a dropped link delivers nothing of what j sent during tick t-1 to i: not its ACCLAIM + COORDINATOR pair,
+ * not its HEARTBEAT (no liveness proof, no leader position, no bully-back), not its TASK_CLAIMs, not its
+ * TASK_CONFLICTs.  Every other step is swarm_update_loop_radio's / swarm_update_loop_tasks': the walk order,
+ * the lagged positions, timers, the claim evaluation, kills, the refusal of a too-dense tick.  j -> i and
+ * i -> j are decided independently.  The draw, in uint64_t arithmetic mod 2^64:
+ *     fin(x): x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9; x = (x ^ (x >> 27)) * 0x94D049BB133111EB; x ^ (x >> 31)
+ *     a = fin(seed ^ (u64(u32(sid)) * 0x9E3779B97F4A7C15) ^ (u64(t) * 0xD1B54A32D192ED03))
+ *     b = fin(a ^ (u64(u32(rid)) * 0x9E3779B97F4A7C15));  u = double(b >> 11) * 2^-53
+ * It is keyed on IDs, not storage indices, and on the absolute tick: the decisions depend neither on the layout
+ * nor on how a run is cut into calls, and there is no per-agent state.  The granularity is the link and the
+ * tick, not the packet: the receive fuses a sender's ACCLAIM with the COORDINATOR that follows it, and the task
+ * tick relies on the election handlers only ever leaving FOLLOWER behind.
+ * Arguments: swarm_update_loop_tasks', then ch and link_counts.  tasks == NULL or tasks->T == 0: the radio loop
+ * (task_counts zeroed, *n_guard = 0).  ch == NULL or ch->loss == 0.0: swarm_update_loop_radio's /
+ * swarm_update_loop_tasks' own kernels and bits, and link_counts is NOT written (those kernels do not count
+ * links).  link_counts (host, ticks x 2, may be NULL), written when ch->loss > 0: per tick [0] the election
+ * links -- ordered pairs of an alive receiver and an in-range sender j != i whose tick t-1 sends include an
+ * ACCLAIM or a HEARTBEAT -- and [1] how many of those were dropped.  Claim-only and conflict-only senders are
+ * not counted; they are dropped by the same rule.  A refused tick withholds link_counts (zeros).
+ * SWARM_ERR_ARG (nothing written): ch->loss NaN, < 0 or > 1, and whatever the two loops refuse.
+ * swarm_link_dropped: the rule on the host, 1 when the link is dropped, else 0 (needs no device).
+ */
+typedef struct {
+    double loss;
+    uint64_t seed;
+} swarm_channel;
+
+int swarm_update_loop_channel(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                              const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                              double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                              int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                              const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                              double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                              int64_t *refused_tick, const swarm_tasks *tasks, int64_t *task_counts,
+                              int64_t *n_guard, void *stream, const swarm_channel *ch, int64_t *link_counts);
+
+int swarm_link_dropped(uint64_t seed, int64_t t, int32_t sid, int32_t rid, double loss);
+
+/*
  * Obstacle fields (contract O1): the sensed physics visits only the obstacles in reach.
  * A field is built once from a list of m obstacles (x, y, r) and is read-only afterwards.  It owns a device
  * copy of the list and, over a uniform grid that covers the obstacles' footprints, for every cell the
