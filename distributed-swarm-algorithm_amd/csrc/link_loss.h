@@ -29,4 +29,25 @@ __host__ __device__ __forceinline__ bool link_dropped(uint64_t seed, int64_t t, 
     return link_u(seed, t, sid, rid) < loss;
 }
 
+// The channel as the window kernels of protocol.hip take it: their last parameter, its type their template
+// parameter.  The link j -> i of tick t is dropped iff dropped(t, ids[j], ids[i]), and a dropped link delivers
+// nothing of j's tick t-1 sends.  NoLoss is empty and what `if constexpr (Ch::kLossy)` guards is not compiled
+// for it, so k_*<NoLoss> has the instructions of a kernel written without a channel (kernel-argument offsets
+// aside; tools/asm_compare.py).  The tick stays the kernels' own argument, not a field of Lossy: the lossy
+// instantiations depend on that for their registers.
+struct NoLoss {
+    static constexpr bool kLossy = false;
+};
+struct Lossy {
+    static constexpr bool kLossy = true;
+    double loss;
+    uint64_t seed;
+    // the tick's kShards x 4 link counters: [0] the election links (alive receiver, in-range sender with an
+    // ACCLAIM or a HEARTBEAT), [1] those of them that were dropped
+    unsigned long long *cnt;
+    __device__ bool dropped(int64_t t, int32_t sid, int32_t rid) const {
+        return link_dropped(seed, t, sid, rid, loss);
+    }
+};
+
 }  // namespace swarm

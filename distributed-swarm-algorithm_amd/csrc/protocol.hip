@@ -45,11 +45,14 @@
 // agent with the row walk replaced by the receive over its 3 x 3 cell window of the same binning (hear_window).
 // swarm_update_loop_tasks (U1-T) is the radio loop with _process_tasks and the two task handlers run every tick:
 // k_radio_outbox<true>, k_task_conflicts and k_tick_radio_tasks in place of the two radio kernels (TaskState).
+// swarm_update_loop_channel (U1-L) is either of the two over a lossy channel: the three kernels that hear are
+// templates on the channel (link_loss.h), k_*<NoLoss> what the loss-free loops launch, k_*<Lossy> what it adds.
 // The four tick kernels (k_tick_pull, k_tick, k_tick_radio, k_tick_radio_tasks) differ in how an agent receives;
 // what follows the receive is one function (settle_agent), and the two window kernels share the receive too.
-// The host loop of all six entry points is run_ticks, a sequence of stages that each own their scratch:
-// check_run_args, Counters, pack_records, PushState / RadioState / TaskState / launch_tick_pull (the receive launch by
-// mode), EntrySnapshot (sensed), TickClocks (A/B aid), tick_physics, read_back (one host wait).
+// The host loop of every entry point is run_ticks, a sequence of stages that each own their scratch:
+// check_run_args, Counters (TickSums: a run's per-tick counters, also the task and link counts), pack_records,
+// PushState / RadioState / TaskState / launch_tick_pull (the receive launch by mode), EntrySnapshot (sensed),
+// TickClocks (A/B aid), tick_physics, read_back (one host wait).
 #include <cmath>
 #include <cstring>
 
@@ -977,64 +980,22 @@ __device__ __forceinline__ void hear_window(double2 p, int64_t i, const Radio &w
     }
 }
 
-// The channel of a lossy tick (contract U1-L; link_loss.h): the link j -> i is dropped at tick t iff
-// link_dropped(seed, t, ids[j], ids[i], loss), and a dropped link delivers nothing of j's tick t-1 sends.  cnt:
-// the tick's kShards x 4 link counters -- [0] the election links (alive receiver, in-range sender with an
-// ACCLAIM or a HEARTBEAT), [1] those of them that were dropped.  The lossy kernels are siblings of the
-// plain ones, which keep their instructions.
-struct Lossy {
-    double loss;
-    uint64_t seed;
-    unsigned long long *cnt;
-};
-
 // k_tick_pull's agent over the window: threads in cell-sorted order (a wave's lanes share their windows and
 // the nine sender bytes; the records are gathered by storage index), the row walk replaced by hear_window.
-// Returns at once when a tick of the call was refused (the caller restores every array).
+// Returns at once when a tick of the call was refused (the caller restores every array).  Over a lossy channel
+// hear_window's `sender` judges the link first, counts it, and returns when it is dropped.
+template <class Ch>
 __global__ __launch_bounds__(kBlock) void k_tick_radio(int64_t n, int64_t t, const int32_t *__restrict__ ids,
                                                       const double2 *__restrict__ pos, Fsm f, Radio w,
                                                       uint8_t *__restrict__ ob_out, double dt, double timeout,
                                                       double jitter, uint64_t seed,
-                                                      unsigned long long *__restrict__ counts) {
-    __shared__ unsigned s_cnt[4];
+                                                      unsigned long long *__restrict__ counts, Ch ch) {
+    __shared__ unsigned s_cnt[4], s_lcnt[Ch::kLossy ? 4 : 1];
     if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const double now = double(t) * dt;
-    TickCounts c;
-    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
-        const int64_t i = w.sorted[q0];
-        const uint2 r = f.rec[i];
-        if (!fw_alive(r.x)) {
-            ob_out[i] = 0;
-            continue;
-        }
-        const double2 p = w.psort[q0];
-        const int32_t me = ids[i];
-        const bool hb_tick = ((t + fw_phase(r.x)) % 10) == 0;
-        uint32_t bits = fw_bits(r.x);
-        int32_t y = int32_t(r.y);
-        Heard h{fw_state(r.x), 0, false, false, 0, -1};
-        // (0xFF, not the two outbox bits: the pass wrote the byte masked, the `&` folds away)
-        hear_window(p, i, w, 0xFF, ids, [&](int64_t cell) { return w.cell_send[cell]; },
-                    [&](uint8_t o, int32_t sid, int32_t j) { hear(h, o, sid, j, me, hb_tick); });
-        apply_heard(i, h, t, pos, f, bits, y);
-        ob_out[i] = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
+    if (threadIdx.x < 4) {
+        s_cnt[threadIdx.x] = 0;
+        if constexpr (Ch::kLossy) s_lcnt[threadIdx.x] = 0;
     }
-    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
-}
-
-// k_tick_radio over a lossy channel: hear_window's `sender` judges the link first, counts it, and returns when
-// it is dropped.  (A copy of k_tick_radio's text, not one template for both: with the two folded into one body
-// the plain kernel came out with another register allocation, and it has to keep its instructions.)
-__global__ __launch_bounds__(kBlock) void k_tick_radio_lossy(int64_t n, int64_t t, const int32_t *__restrict__ ids,
-                                                            const double2 *__restrict__ pos, Fsm f, Radio w,
-                                                            uint8_t *__restrict__ ob_out, double dt, double timeout,
-                                                            double jitter, uint64_t seed,
-                                                            unsigned long long *__restrict__ counts, Lossy ch) {
-    __shared__ unsigned s_cnt[4], s_lcnt[4];
-    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = s_lcnt[threadIdx.x] = 0;
     __syncthreads();
     const double now = double(t) * dt;
     TickCounts c;
@@ -1055,16 +1016,19 @@ __global__ __launch_bounds__(kBlock) void k_tick_radio_lossy(int64_t n, int64_t 
         // (0xFF, not the two outbox bits: the pass wrote the byte masked, the `&` folds away)
         hear_window(p, i, w, 0xFF, ids, [&](int64_t cell) { return w.cell_send[cell]; },
                     [&](uint8_t o, int32_t sid, int32_t j) {
-                        const bool drop = link_dropped(ch.seed, t, sid, me, ch.loss);
-                        ++links;  // every sender of this window sent an election packet
-                        lost += drop;
-                        if (!drop) hear(h, o, sid, j, me, hb_tick);
+                        if constexpr (Ch::kLossy) {
+                            const bool drop = ch.dropped(t, sid, me);
+                            ++links;  // every sender of this window sent an election packet
+                            lost += drop;
+                            if (drop) return;
+                        }
+                        hear(h, o, sid, j, me, hb_tick);
                     });
         apply_heard(i, h, t, pos, f, bits, y);
         ob_out[i] = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
     }
     add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
-    add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
+    if constexpr (Ch::kLossy) add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
 }
 
 // ---------------------------------------------------------------- task update loop (contract U1-T)
@@ -1126,9 +1090,15 @@ __global__ __launch_bounds__(kBlock) void k_task_sender_bytes(int64_t n2, const 
 }
 
 // _handle_task_conflict (327-336) for every alive agent, over the conflict senders it hears, in ascending
-// storage index; within a sender ascending task (one message per task is all that matters: the last).
-__global__ __launch_bounds__(kBlock) void k_task_conflicts(int64_t n, const int32_t *__restrict__ ids,
-                                                          const uint2 *__restrict__ rec, Radio w, TaskTick k) {
+// storage index; within a sender ascending task (one message per task is all that matters: the last).  Over a
+// lossy channel a conflict sender in range is heard only over a link that tick t keeps -- the verdict the tick
+// kernel reaches for the same (t, sender, receiver); the sender's ID is gathered for that alone.  Only then is
+// the tick an argument, k_task_conflicts<Lossy, int64_t>: an unused one would move the loss-free kernel's
+// argument loads if it came second, and in any later place the lossy kernel is allocated other registers.
+template <class Ch, class... Tick>
+__global__ __launch_bounds__(kBlock) void k_task_conflicts(int64_t n, Tick... t, const int32_t *__restrict__ ids,
+                                                          const uint2 *__restrict__ rec, Radio w, TaskTick k,
+                                                          Ch ch) {
     if (w.st[0] != 0) return;
     for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
         const double2 p = w.psort[q0];
@@ -1153,53 +1123,8 @@ __global__ __launch_bounds__(kBlock) void k_task_conflicts(int64_t n, const int3
             const double2 s = w.psort[q];
             const double ex = p.x - s.x, ey = p.y - s.y;
             if (!(ex * ex + ey * ey <= w.r2)) return;
-            unsigned long long m = k.conflict_in[j] & k.tmask;
-            const int32_t *row = k.tab_winner + int64_t(j) * k.T;
-            while (m) {
-                const int t = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const unsigned long long bit = 1ull << t;
-                hi |= bit;  // ASSIGNED (3) for the winner, LOCKED (2) for everyone else
-                lo = row[t] == me ? lo | bit : lo & ~bit;
-            }
-        });
-        if (lo != lo0) k.status_lo[i] = lo;
-        if (hi != hi0) k.status_hi[i] = hi;
-    }
-}
-
-// k_task_conflicts over a lossy channel: a conflict sender in range is heard only over a link that tick t
-// keeps -- the verdict the tick kernel reaches for the same (t, sender, receiver); the sender's ID is gathered
-// for that alone.  (A copy, as k_tick_radio_lossy.)
-__global__ __launch_bounds__(kBlock) void k_task_conflicts_lossy(int64_t n, int64_t t,
-                                                                const int32_t *__restrict__ ids,
-                                                                const uint2 *__restrict__ rec, Radio w, TaskTick k,
-                                                                Lossy ch) {
-    if (w.st[0] != 0) return;
-    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
-        const double2 p = w.psort[q0];
-        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
-        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
-        uint8_t any = 0;  // the nine bytes loaded at once
-#pragma unroll
-        for (int c = 0; c < 9; ++c) {
-            const int64_t yy = cy + (c / 3) - 1, xx = cx + (c % 3) - 1;
-            const bool in = yy >= 0 && yy < w.g.ncy && xx >= 0 && xx < w.g.ncx;
-            const uint8_t fl = k.cell_conf[in ? yy * w.g.ncx + xx : 0];
-            any |= in ? fl : uint8_t(0);
-        }
-        if (!any) continue;
-        const int64_t i = w.sorted[q0];
-        if (!fw_alive(rec[i].x)) continue;
-        const int32_t me = ids[i];
-        const unsigned long long lo0 = k.status_lo[i], hi0 = k.status_hi[i];
-        unsigned long long lo = lo0, hi = hi0;
-        window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
-            if (!(w.ob_sorted[q] & kConflict) || j == int32_t(i)) return;
-            const double2 s = w.psort[q];
-            const double ex = p.x - s.x, ey = p.y - s.y;
-            if (!(ex * ex + ey * ey <= w.r2)) return;
-            if (link_dropped(ch.seed, t, ids[j], me, ch.loss)) return;
+            if constexpr (Ch::kLossy)
+                if (ch.dropped(t..., ids[j], me)) return;
             unsigned long long m = k.conflict_in[j] & k.tmask;
             const int32_t *row = k.tab_winner + int64_t(j) * k.T;
             while (m) {
@@ -1288,106 +1213,22 @@ __device__ __forceinline__ unsigned long long wave_tasks(double2 p, int T, const
 
 // At >= 4 waves per SIMD (128 VGPRs, none spilled): leg (a) of tools/bench_loop_tasks.py 4.28-4.30 ms per tick
 // against 4.44-4.46 at the compiler's 3 (138 VGPRs), same session; 5 waves would need scratch (38 VGPRs spilled).
+// Over a lossy channel the link is judged before the sender's election packets and claims are handled.
+template <class Ch>
 __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64_t t, const int32_t *__restrict__ ids,
                                                             const double2 *__restrict__ pos, Fsm f, Radio w,
                                                             uint8_t *__restrict__ ob_out, double dt, double timeout,
                                                             double jitter, uint64_t seed,
-                                                            unsigned long long *__restrict__ counts, TaskTick k) {
-    __shared__ unsigned s_cnt[4], s_tcnt[4];
+                                                            unsigned long long *__restrict__ counts, TaskTick k,
+                                                            Ch ch) {
+    __shared__ unsigned s_cnt[4], s_tcnt[4], s_lcnt[Ch::kLossy ? 4 : 1];
     __shared__ double s_tx[kMaxTasks], s_ty[kMaxTasks];
     __shared__ int8_t s_rq[kMaxTasks];
     if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = s_tcnt[threadIdx.x] = 0;
-    if (int(threadIdx.x) < k.T) {
-        const double2 q = k.tpos[threadIdx.x];
-        s_tx[threadIdx.x] = q.x;
-        s_ty[threadIdx.x] = q.y;
-        s_rq[threadIdx.x] = k.treq[threadIdx.x];
+    if (threadIdx.x < 4) {
+        s_cnt[threadIdx.x] = s_tcnt[threadIdx.x] = 0;
+        if constexpr (Ch::kLossy) s_lcnt[threadIdx.x] = 0;
     }
-    __syncthreads();
-    const double now = double(t) * dt;
-    TickCounts c;
-    unsigned c_claim = 0, c_guard = 0;
-    ClaimRx cr{k.claim_in, pos, k.caps, nullptr, nullptr, s_tx, s_ty, s_rq, 0ull, 0u, 0u, k.tmask};
-    // (the trip count is uniform over the workgroup: every wave enters wave_tasks with all its lanes)
-    for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += int64_t(gridDim.x) * kBlock) {
-        const int64_t q0 = base + threadIdx.x;
-        const bool valid = q0 < n;
-        const double2 p = valid ? w.psort[q0] : make_double2(kNaN, kNaN);
-        const unsigned long long reach = wave_tasks(p, k.T, s_tx, s_ty);
-        if (!valid) continue;
-        const int64_t i = w.sorted[q0];
-        const uint2 r = f.rec[i];
-        const uint32_t fw = r.x;
-        const uint8_t old = k.sb_out[i];  // what this slot's words hold (tick t-2's sends)
-        if (!fw_alive(fw)) {
-            ob_out[i] = 0;
-            if (old & kClaim) k.claim_out[i] = 0;
-            if (old & kConflict) k.conflict_out[i] = 0;
-            if (old) k.sb_out[i] = 0;
-            continue;
-        }
-        const int32_t me = ids[i];
-        const uint8_t st0 = fw_state(fw);
-        const bool hb_tick = ((t + fw_phase(fw)) % 10) == 0;
-        uint32_t bits = fw_bits(fw);
-        int32_t y = int32_t(r.y);
-        Heard h{st0, 0, false, false, 0, -1};
-        // only a LEADER's walk looks at claims (see the header)
-        const bool lead0 = st0 == ST_L;
-        const uint8_t rel = uint8_t(kAcclaim | kHeartbeat | (lead0 ? kClaim : 0));
-        cr.tw = k.tab_winner + i * k.T;
-        cr.tu = k.tab_util + i * k.T;
-        cr.conf = 0;
-        hear_window(
-            p, i, w, rel, ids,
-            [&](int64_t cell) { return uint8_t(w.cell_send[cell] | (lead0 ? k.cell_claim[cell] : uint8_t(0))); },
-            [&](uint8_t o, int32_t sid, int32_t j) {
-                hear(h, o, sid, j, me, hb_tick);
-                if ((o & kClaim) && h.st == ST_L) hear_claims(cr, j, sid);
-            });
-        apply_heard(i, h, t, pos, f, bits, y);
-        const uint8_t ob = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
-        ob_out[i] = ob;
-        // _process_tasks (292-302): the tasks still OPEN after this tick's conflicts, at the tick's snapshot;
-        // the status is read only when a task is near the wave at all
-        unsigned long long claims = 0;
-        if (reach) {
-            const unsigned long long lo = k.status_lo[i];
-            unsigned long long open = ~(lo | k.status_hi[i]) & reach;
-            const uint32_t cp = k.caps[i];
-            while (open) {
-                const int a = __ffsll((long long)open) - 1;
-                open &= open - 1;
-                const double dx = p.x - s_tx[a], dy = p.y - s_ty[a];
-                if (!(dx * dx + dy * dy <= kClaimFar2)) continue;
-                const double U = utility(p.x, p.y, cp, s_tx[a], s_ty[a], s_rq[a], kUScale);
-                c_guard += guard_flag(U, kClaimThr);
-                if (U > kClaimThr) claims |= 1ull << a;
-            }
-            if (claims) k.status_lo[i] = lo | claims;  // TENTATIVE
-        }
-        if (claims || (old & kClaim)) k.claim_out[i] = claims;
-        if (cr.conf || (old & kConflict)) k.conflict_out[i] = cr.conf;
-        const uint8_t sent = uint8_t(ob | (claims ? kClaim : 0) | (cr.conf ? kConflict : 0));
-        if (sent != old) k.sb_out[i] = sent;
-        c_claim += unsigned(__popcll(claims));
-    }
-    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
-    add_counts(c_claim, cr.handled, cr.sent, c_guard, s_tcnt, k.cnt);
-}
-
-// k_tick_radio_tasks over a lossy channel: the link is judged before the sender's election packets and claims
-// are handled.  (A copy, as k_tick_radio_lossy.)
-__global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks_lossy(
-    int64_t n, int64_t t, const int32_t *__restrict__ ids, const double2 *__restrict__ pos, Fsm f, Radio w,
-    uint8_t *__restrict__ ob_out, double dt, double timeout, double jitter, uint64_t seed,
-    unsigned long long *__restrict__ counts, TaskTick k, Lossy ch) {
-    __shared__ unsigned s_cnt[4], s_tcnt[4], s_lcnt[4];
-    __shared__ double s_tx[kMaxTasks], s_ty[kMaxTasks];
-    __shared__ int8_t s_rq[kMaxTasks];
-    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
-    if (threadIdx.x < 4) s_cnt[threadIdx.x] = s_tcnt[threadIdx.x] = s_lcnt[threadIdx.x] = 0;
     if (int(threadIdx.x) < k.T) {
         const double2 q = k.tpos[threadIdx.x];
         s_tx[threadIdx.x] = q.x;
@@ -1433,12 +1274,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks_lossy(
             p, i, w, rel, ids,
             [&](int64_t cell) { return uint8_t(w.cell_send[cell] | (lead0 ? k.cell_claim[cell] : uint8_t(0))); },
             [&](uint8_t o, int32_t sid, int32_t j) {
-                // (a claim-only sender is no election link; it is dropped all the same)
-                const bool drop = link_dropped(ch.seed, t, sid, me, ch.loss);
-                const unsigned el = (o & (kAcclaim | kHeartbeat)) != 0;
-                links += el;
-                lost += el & unsigned(drop);
-                if (drop) return;
+                if constexpr (Ch::kLossy) {
+                    // (a claim-only sender is no election link; it is dropped all the same)
+                    const bool drop = ch.dropped(t, sid, me);
+                    const unsigned el = (o & (kAcclaim | kHeartbeat)) != 0;
+                    links += el;
+                    lost += el & unsigned(drop);
+                    if (drop) return;
+                }
                 hear(h, o, sid, j, me, hb_tick);
                 if ((o & kClaim) && h.st == ST_L) hear_claims(cr, j, sid);
             });
@@ -1471,11 +1314,11 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks_lossy(
     }
     add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
     add_counts(c_claim, cr.handled, cr.sent, c_guard, s_tcnt, k.cnt);
-    add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
+    if constexpr (Ch::kLossy) add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
 }
 
 // ---------------------------------------------------------------- the host loop, in stages
-// One run's arguments, as the five entry points fill them (`loop`: swarm_update_loop*, each tick then followed
+// One run's arguments, as the entry points fill them (`loop`: swarm_update_loop*, each tick then followed
 // by its physics step; `pos` is not used then, the heartbeats read the lagged buffer).
 struct TickRun {
     swarm_ctx *ctx;
@@ -1535,23 +1378,44 @@ int check_run_args(const TickRun &r) {
     return SWARM_OK;
 }
 
+// Four counters per tick of the run in one scratch slot: per tick kShards x 4 partial counters (add_counts),
+// cleared, then per tick their 4 sums (k_sum_counts), then `extra` bytes of the owner's.
+struct TickSums {
+    unsigned long long *part = nullptr, *sums = nullptr;
+    int64_t t0 = 0, ticks = 0;
+
+    int begin(const TickRun &r, Slot slot, hipStream_t s, size_t extra = 0) {
+        t0 = r.t0;
+        ticks = r.ticks;
+        const size_t part_bytes = size_t(ticks) * kShards * 4 * 8;
+        SW_ALLOC(part, r.ctx, slot, part_bytes + bytes() + extra);
+        sums = part + size_t(ticks) * kShards * 4;
+        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
+        return SWARM_OK;
+    }
+    unsigned long long *at(int64_t t) const { return part + size_t(t - t0 - 1) * kShards * 4; }  // tick t's partials
+    size_t bytes() const { return size_t(ticks) * 4 * 8; }                                       // of the sums
+    int sum_into(unsigned long long *host_dst, hipStream_t s) const {
+        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(ticks * 4, kBlock, 256)), dim3(kBlock), 0, s, ticks, part, sums);
+        SW_LAUNCHED();
+        SW_HIP(hipMemcpyAsync(host_dst, sums, bytes(), hipMemcpyDeviceToHost, s));
+        return SWARM_OK;
+    }
+};
+
 // The run's counters in one scratch buffer (S_TMP0), laid out once.
 struct Counters {
-    unsigned long long *part;       // per tick: kShards x 4 partial counters
-    unsigned long long *sums;       // per tick: their 4 sums (k_sum_counts)
+    TickSums tick;                  // lead, wait, acclaims, heartbeats
     unsigned long long *tr_shards;  // kShards x kTraffic traffic counters, NULL when no traffic is asked for
     unsigned long long *tr_sums;    // their kTraffic sums (k_sum_traffic)
     unsigned long long *sing;       // the loop's singular count: the last 64 bytes of the buffer
     int lay(const TickRun &r, hipStream_t s) {
-        const size_t ticks = size_t(r.ticks);
-        const size_t part_bytes = ticks * kShards * 4 * 8, tr_bytes = size_t(kShards) * kTraffic * 8;
-        SW_ALLOC(part, r.ctx, S_TMP0, part_bytes + ticks * 4 * 8 + tr_bytes + kTraffic * 8 + 64);
-        sums = part + ticks * kShards * 4;
-        unsigned long long *shards = sums + ticks * 4;
+        const size_t tr_bytes = size_t(kShards) * kTraffic * 8;
+        if (const int rc = tick.begin(r, S_TMP0, s, tr_bytes + kTraffic * 8 + 64)) return rc;
+        unsigned long long *shards = tick.sums + tick.ticks * 4;
         tr_shards = r.traffic ? shards : nullptr;
         tr_sums = shards + size_t(kShards) * kTraffic;
         sing = tr_sums + kTraffic;
-        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
         if (tr_shards) SW_HIP(hipMemsetAsync(tr_shards, 0, tr_bytes, s));
         if (r.loop) SW_HIP(hipMemsetAsync(sing, 0, 8, s));
         return SWARM_OK;
@@ -1654,57 +1518,38 @@ struct RadioState {
         return SWARM_OK;
     }
 
-    // ch: the tick's channel on a lossy run (LinkState::of), else NULL
-    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, const Lossy *ch, hipStream_t s) {
-        const dim3 grid(grid_for(r.n, kBlock, 8192));
+    // the tick's binning: rebuilt by loop_sense_tick before every tick's launches
+    void bind(const LoopSense &ls) {
         rw.sorted = ls.sorted;
         rw.off = ls.off;
         rw.psort = ls.psort;
+    }
+
+    // ch: NoLoss{}, or the tick's Lossy
+    template <class Ch>
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, Ch ch, hipStream_t s) const {
+        const dim3 grid(grid_for(r.n, kBlock, 8192));
         SW_HIP(hipMemsetAsync(rw.cell_send, 0, cells, s));
         hipLaunchKernelGGL(k_radio_outbox<false>, grid, dim3(kBlock), 0, s, r.n, k.ob_in, rw, (uint8_t *)nullptr,
                            (uint8_t *)nullptr);
         SW_LAUNCHED();
-        if (ch)
-            hipLaunchKernelGGL(k_tick_radio_lossy, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out,
-                               r.dt, r.timeout, r.jitter, r.seed, k.cnt, *ch);
-        else
-            hipLaunchKernelGGL(k_tick_radio, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
-                               r.timeout, r.jitter, r.seed, k.cnt);
+        hipLaunchKernelGGL(k_tick_radio<Ch>, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rw, k.ob_out, r.dt,
+                           r.timeout, r.jitter, r.seed, k.cnt, ch);
         SW_LAUNCHED();
         return SWARM_OK;
     }
 };
 
-// A lossy run (U1-L): the per-tick link counters, sharded and summed as the tick counts.
-struct LinkState {
-    unsigned long long *part = nullptr, *sums = nullptr;
-
-    int begin(const TickRun &r, hipStream_t s) {
-        const size_t ticks = size_t(r.ticks), part_bytes = ticks * kShards * 4 * 8;
-        SW_ALLOC(part, r.ctx, S_LINK_COUNTS, part_bytes + ticks * 4 * 8);
-        sums = part + ticks * kShards * 4;
-        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
-        return SWARM_OK;
-    }
-
-    Lossy of(const TickRun &r, int64_t t) const {
-        return Lossy{r.ch->loss, r.ch->seed, part + size_t(t - r.t0 - 1) * kShards * 4};
-    }
-};
-
-// Task mode (U1-T): RadioState's scratch with three bytes per cell, the per-tick task counters (sharded as the
-// tick counts, the fourth the guard pairs) and the tick's three launches.
+// Task mode (U1-T): RadioState's scratch with three bytes per cell, the per-tick task counters (claims sent,
+// handled, conflicts sent, guard pairs) and the tick's three launches.
 struct TaskState {
-    unsigned long long *part = nullptr, *sums = nullptr;
+    TickSums cnt;
     uint8_t *sb = nullptr;  // the sender bytes, 2n by tick parity (TaskTick)
     unsigned long long tmask = 0;
 
     int begin(const TickRun &r, hipStream_t s) {
-        const size_t ticks = size_t(r.ticks), part_bytes = ticks * kShards * 4 * 8;
         const swarm_tasks &b = *r.tasks;
-        SW_ALLOC(part, r.ctx, S_TASK_COUNTS, part_bytes + ticks * 4 * 8);
-        sums = part + ticks * kShards * 4;
-        SW_HIP(hipMemsetAsync(part, 0, part_bytes, s));
+        if (const int rc = cnt.begin(r, S_TASK_COUNTS, s)) return rc;
         SW_ALLOC(sb, r.ctx, S_TASK_SENDERS, size_t(r.n) * 2);
         tmask = b.T >= 64 ? ~0ull : (1ull << b.T) - 1ull;
         hipLaunchKernelGGL(k_task_sender_bytes, dim3(grid_for(2 * r.n, kBlock, 8192)), dim3(kBlock), 0, s, 2 * r.n,
@@ -1714,15 +1559,13 @@ struct TaskState {
         return SWARM_OK;
     }
 
-    int launch(const TickRun &r, const Fsm &f, const Tick &k, const LoopSense &ls, RadioState &rs, const Lossy *ch,
-               hipStream_t s) {
+    // rs: bound to the tick's binning; ch: NoLoss{}, or the tick's Lossy
+    template <class Ch>
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, const RadioState &rs, Ch ch, hipStream_t s) const {
         const dim3 grid(grid_for(r.n, kBlock, 8192));
         const swarm_tasks &b = *r.tasks;
         const size_t un = size_t(r.n), in = size_t((k.t - 1) & 1) * un, out = size_t(k.t & 1) * un;
         auto u64 = [](uint64_t *p) { return reinterpret_cast<unsigned long long *>(p); };
-        rs.rw.sorted = ls.sorted;
-        rs.rw.off = ls.off;
-        rs.rw.psort = ls.psort;
         const TaskTick tk{b.T,
                           tmask,
                           reinterpret_cast<const double2 *>(b.tpos),
@@ -1738,25 +1581,21 @@ struct TaskState {
                           b.tab_util,
                           rs.rw.cell_send + rs.cells,
                           rs.rw.cell_send + 2 * rs.cells,
-                          part + size_t(k.t - r.t0 - 1) * kShards * 4,
+                          cnt.at(k.t),
                           sb + in,
                           sb + out};
         SW_HIP(hipMemsetAsync(rs.rw.cell_send, 0, 3 * rs.cells, s));
         hipLaunchKernelGGL(k_radio_outbox<true>, grid, dim3(kBlock), 0, s, r.n, tk.sb_in, rs.rw, tk.cell_claim,
                            tk.cell_conf);
         SW_LAUNCHED();
-        if (ch)
-            hipLaunchKernelGGL(k_task_conflicts_lossy, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec, rs.rw, tk,
-                               *ch);
+        if constexpr (Ch::kLossy)
+            hipLaunchKernelGGL((k_task_conflicts<Ch, int64_t>), grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec,
+                               rs.rw, tk, ch);
         else
-            hipLaunchKernelGGL(k_task_conflicts, grid, dim3(kBlock), 0, s, r.n, r.ids, f.rec, rs.rw, tk);
+            hipLaunchKernelGGL(k_task_conflicts<Ch>, grid, dim3(kBlock), 0, s, r.n, r.ids, f.rec, rs.rw, tk, ch);
         SW_LAUNCHED();
-        if (ch)
-            hipLaunchKernelGGL(k_tick_radio_tasks_lossy, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
-                               k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk, *ch);
-        else
-            hipLaunchKernelGGL(k_tick_radio_tasks, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
-                               k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk);
+        hipLaunchKernelGGL(k_tick_radio_tasks<Ch>, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
+                           k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, tk, ch);
         SW_LAUNCHED();
         return SWARM_OK;
     }
@@ -1889,7 +1728,7 @@ int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t,
 // run's one final host wait (none when nothing is asked for).  A refused tick (`snap` restores the caller's
 // arrays) withholds the counts and the singular count and sets refused_tick.
 int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap,
-              const TaskState &ts, const LinkState &lk, hipStream_t s) {
+              const TickSums &tasks, const TickSums &links, hipStream_t s) {
     const bool want_sing = r.loop && r.loop->n_singular;
     const bool want_tasks = r.tasked() && (r.task_counts || r.n_guard);
     const bool want_links = r.lossy() && r.link_counts;
@@ -1900,34 +1739,19 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
     if (ls)
         if (const int rc = snap.restore_if_refused(ls->st, s)) return rc;
     if (!(r.traffic || ls || want_sing || r.counts || want_tasks || want_links)) return SWARM_OK;
-    const size_t cnt_bytes = r.counts ? size_t(r.ticks) * 4 * 8 : 0;
-    const size_t tcnt_bytes = want_tasks ? size_t(r.ticks) * 4 * 8 : 0;  // after the counts
-    const size_t lcnt_bytes = want_links ? size_t(r.ticks) * 4 * 8 : 0;  // after the task counts
-    unsigned long long *h =
-        static_cast<unsigned long long *>(pinned(r.ctx, 128 + cnt_bytes + tcnt_bytes + lcnt_bytes));
+    // the sums that are asked for, one after the other from [16]: counts, task counts, link counts
+    const size_t words = size_t(r.ticks) * 4, cnt_bytes = r.counts ? words * 8 : 0;
+    unsigned long long *h = static_cast<unsigned long long *>(
+        pinned(r.ctx, 128 + cnt_bytes + (size_t(want_tasks) + size_t(want_links)) * words * 8));
     if (!h) return SWARM_ERR_OOM;
-    unsigned long long *ht = h + 16 + cnt_bytes / 8, *hl = ht + tcnt_bytes / 8;
-    if (want_links) {
-        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
-                           int64_t(r.ticks), lk.part, lk.sums);
-        SW_LAUNCHED();
-        SW_HIP(hipMemcpyAsync(hl, lk.sums, lcnt_bytes, hipMemcpyDeviceToHost, s));
-    }
-    if (want_tasks) {
-        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
-                           int64_t(r.ticks), ts.part, ts.sums);
-        SW_LAUNCHED();
-        SW_HIP(hipMemcpyAsync(ht, ts.sums, tcnt_bytes, hipMemcpyDeviceToHost, s));
-    }
+    unsigned long long *ht = h + 16 + cnt_bytes / 8, *hl = ht + (want_tasks ? words : 0);
+    int rc;
+    if (want_links && (rc = links.sum_into(hl, s))) return rc;
+    if (want_tasks && (rc = tasks.sum_into(ht, s))) return rc;
     if (r.traffic) SW_HIP(hipMemcpyAsync(h + 8, c.tr_sums, kTraffic * 8, hipMemcpyDeviceToHost, s));
     if (ls) SW_HIP(hipMemcpyAsync(h, ls->st, 32, hipMemcpyDeviceToHost, s));
     if (want_sing) SW_HIP(hipMemcpyAsync(h + 4, c.sing, 8, hipMemcpyDeviceToHost, s));
-    if (r.counts) {
-        hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(int64_t(r.ticks) * 4, kBlock, 256)), dim3(kBlock), 0, s,
-                           int64_t(r.ticks), c.part, c.sums);
-        SW_LAUNCHED();
-        SW_HIP(hipMemcpyAsync(h + 16, c.sums, cnt_bytes, hipMemcpyDeviceToHost, s));
-    }
+    if (r.counts && (rc = c.tick.sum_into(h + 16, s))) return rc;
     SW_HIP(hipStreamSynchronize(s));
     if (r.traffic) for (int q = 0; q < kTraffic; ++q) r.traffic[q] = int64_t(h[8 + q]);
     if (ls && h[0]) {
@@ -1986,20 +1810,20 @@ int run_ticks(const TickRun &r) {
     PushState ps;
     RadioState rs;
     TaskState ts;
-    LinkState lk;
+    TickSums links;  // a lossy run (U1-L): per tick the election links and those of them that were dropped
     TickClocks clk;
     if (push && (rc = ps.begin(r, grid, s))) return rc;
     if ((rc = clk.begin(r, ps, s))) return rc;
     if (radio && (rc = rs.begin(r, ls, tasked ? 3 : 1))) return rc;
     if (tasked && (rc = ts.begin(r, s))) return rc;
     const bool lossy = radio && r.lossy();
-    if (lossy && (rc = lk.begin(r, s))) return rc;
+    if (lossy && (rc = links.begin(r, S_LINK_COUNTS, s))) return rc;
     double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
     for (int64_t t = r.t0 + 1; t <= r.t0 + r.ticks; ++t) {
         // (a heartbeat sent during tick t-1 carries its sender's position of then: the loops' lagged buffer)
         const Tick k{t, reinterpret_cast<const double2 *>(loop ? lag : r.pos),
                      r.fsm->outbox + size_t((t - 1) & 1) * size_t(r.n), r.fsm->outbox + size_t(t & 1) * size_t(r.n),
-                     cnt.part + size_t(t - r.t0 - 1) * kShards * 4};
+                     cnt.tick.at(t)};
         if (std::find(r.kill_ticks, r.kill_ticks + r.n_kill, t) != r.kill_ticks + r.n_kill) {
             hipLaunchKernelGGL(k_kill_leaders, dim3(grid), dim3(kBlock), 0, s, r.n, f.rec);
             SW_LAUNCHED();
@@ -2007,11 +1831,12 @@ int run_ticks(const TickRun &r) {
         // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell (the call's grid reaches
         // far beyond the agents: offsets by search)
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
-        const Lossy ch = lossy ? lk.of(r, t) : Lossy{};
-        rc = tasked ? ts.launch(r, f, k, ls, rs, lossy ? &ch : nullptr, s)
-             : radio  ? rs.launch(r, f, k, ls, lossy ? &ch : nullptr, s)
-             : push ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
-                    : launch_tick_pull(r, grid, f, k, s);
+        if (radio) rs.bind(ls);
+        auto window_tick = [&](auto ch) { return tasked ? ts.launch(r, f, k, rs, ch, s) : rs.launch(r, f, k, ch, s); };
+        rc = lossy   ? window_tick(Lossy{r.ch->loss, r.ch->seed, links.at(t)})
+             : radio ? window_tick(NoLoss{})
+             : push  ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
+                     : launch_tick_pull(r, grid, f, k, s);
         if (rc) return rc;
         if (loop && (rc = tick_physics(r, f, ls, t, &cur, &lag, cnt.sing, s))) return rc;
     }
@@ -2024,7 +1849,7 @@ int run_ticks(const TickRun &r) {
     hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, r.fsm->state, r.fsm->alive,
                        r.fsm->has_leader_pos, r.fsm->leader, reinterpret_cast<float2 *>(r.fsm->leader_pos), f);
     SW_LAUNCHED();
-    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts, lk, s);
+    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts.cnt, links, s);
 }
 
 // The three loop entry points' own arguments (run_ticks checks the rest): U1 takes a sensor CSR and n < 2^31,
@@ -2171,12 +1996,9 @@ int swarm_update_loop_tasks(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
     if (const int rc = check_tasks(ctx, n, tasks, stream)) return rc;
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
                         trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
-    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
-              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream};
-    r.tasks = tasks;
-    r.task_counts = task_counts;
-    r.n_guard = n_guard;
-    return run_loop(kLoopRadio, r);
+    return run_loop(kLoopRadio, {ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+                                 timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream,
+                                 tasks, task_counts, n_guard});
 }
 
 int swarm_update_loop_channel(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
@@ -2193,14 +2015,9 @@ int swarm_update_loop_channel(swarm_ctx *ctx, int64_t n, const int32_t *ids, dou
         if (const int rc = check_tasks(ctx, n, tasks, stream)) return rc;
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
                         trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
-    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
-              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream};
-    r.tasks = tasks;
-    r.task_counts = task_counts;
-    r.n_guard = n_guard;
-    r.ch = ch;
-    r.link_counts = link_counts;
-    return run_loop(kLoopRadio, r);
+    return run_loop(kLoopRadio, {ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+                                 timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream,
+                                 tasks, task_counts, n_guard, ch, link_counts});
 }
 
 int swarm_link_dropped(uint64_t seed, int64_t t, int32_t sid, int32_t rid, double loss) {

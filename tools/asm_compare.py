@@ -3,13 +3,18 @@
 
     hipcc <the library's flags> -S --cuda-device-only -o A/protocol.s protocol.hip      (one build)
     hipcc ...                                         -o B/protocol.s protocol.hip      (the other)
-    python tools/asm_compare.py A B protocol physics > asm_compare.json
+    python tools/asm_compare.py A B protocol physics [--pair OLD=NEW ...] > asm_compare.json
 
 Per kernel the instructions are compared one by one; directives, comments, labels and blank lines are left
 aside and branch targets are replaced by their number within the kernel.  A kernel only one side has is
 listed as "new" / "gone" with its register, scratch and LDS figures from the compiler's own comments and the
-code object metadata.
+code object metadata.  --pair OLD=NEW (short names as the output prints them, repeatable) compares A's kernel
+OLD with B's kernel NEW: a kernel that was renamed, or became a template's instantiation.  Verdicts: "same";
+"same but kernel-argument offsets" -- equal once the immediate offset of every s_load_dword* (the scalar
+loads that fetch kernel arguments) is masked, what one more or one fewer argument does to a kernel whose
+code is otherwise untouched; "changed", with both sides' figures.
 """
+import argparse
 import json
 import re
 import subprocess
@@ -18,6 +23,7 @@ import sys
 FIG = {"sgprs": r"; TotalNumSgprs: (\d+)", "vgprs": r"; NumVgprs: (\d+)", "agprs": r"; NumAgprs: (\d+)",
        "scratch_bytes": r"; ScratchSize: (\d+)", "lds_bytes": r"; LDSByteSize: (\d+)",
        "occupancy": r"; Occupancy: (\d+)"}
+OFFSETS = "same but kernel-argument offsets"
 
 
 def demangle(names):
@@ -35,7 +41,7 @@ def demangle(names):
     for n, d in zip(names, out):
         d = re.sub(r"\(anonymous namespace\)::", "", d)
         m = re.match(r"(?:void )?(?:swarm::)?([\w:]+(?:<[^(]*>)?)\(", d)
-        short[n] = m.group(1) if m else d
+        short[n] = re.sub(r"\bswarm::", "", m.group(1)) if m else d
     return short
 
 
@@ -71,36 +77,79 @@ def kernels(path):
     return out
 
 
-def main():
-    a_dir, b_dir, files = sys.argv[1], sys.argv[2], sys.argv[3:]
-    res, same, changed, new, gone, lib = {}, 0, [], [], [], {"same": 0, "different": 0}
+def mask_offsets(ins):
+    """The instructions with the immediate offset (the last operand) of every s_load_dword* masked."""
+    return [re.sub(r"^(s_load_dword\w*\s+[^,]+,[^,]+,\s*)(?:offset:)?(?:0x[0-9a-fA-F]+|\d+)\b", r"\1OFF", i)
+            for i in ins]
+
+
+def verdict(a, b):
+    """One kernel of each side, as kernels() gives them."""
+    if a[0] == b[0]:
+        return {"verdict": "same", "instructions": len(a[0])}
+    return {"verdict": OFFSETS if mask_offsets(a[0]) == mask_offsets(b[0]) else "changed",
+            "parent": dict(instructions=len(a[0]), **a[1]), "tree": dict(instructions=len(b[0]), **b[1])}
+
+
+def compare(a_dir, b_dir, files, pairs=()):
+    """The report: `pairs` are (old short name, new short name) of kernels to compare across the two sides."""
+    res, lib = {}, {"same": 0, "different": 0}
+    summary = {"same": 0, OFFSETS: [], "changed": [], "new": [], "gone": []}
+    unused = set(pairs)
+
+    def put(key, v):
+        res[key] = v
+        if v["verdict"] == "same":
+            summary["same"] += 1
+        else:
+            summary[v["verdict"]].append(key)
+
     for f in files:
         a, b = kernels("%s/%s.s" % (a_dir, f)), kernels("%s/%s.s" % (b_dir, f))
         short = demangle(sorted(set(a) | set(b)))
-        for name in sorted(set(a) | set(b), key=lambda q: short[q]):
+        only_a = {short[n]: n for n in a if n not in b}
+        only_b = {short[n]: n for n in b if n not in a}
+        paired = set()
+        for old, new in pairs:
+            if old in only_a and new in only_b:
+                put("%s:%s -> %s" % (f, old, new), verdict(a[only_a[old]], b[only_b[new]]))
+                paired |= {only_a[old], only_b[new]}
+                unused.discard((old, new))
+        for name in sorted((set(a) | set(b)) - paired, key=lambda q: short[q]):
             key = "%s:%s" % (f, short[name])
             if "rocprim" in name or "hipcub" in name:
                 lib["same" if name in a and name in b and a[name][0] == b[name][0] else "different"] += 1
             elif name in a and name in b:
-                if a[name][0] == b[name][0]:
-                    res[key] = {"verdict": "same", "instructions": len(a[name][0])}
-                    same += 1
-                else:
-                    res[key] = {"verdict": "changed", "parent": dict(instructions=len(a[name][0]), **a[name][1]),
-                                "tree": dict(instructions=len(b[name][0]), **b[name][1])}
-                    changed.append(key)
+                put(key, verdict(a[name], b[name]))
             elif name in b:
-                res[key] = {"verdict": "new", "tree": dict(instructions=len(b[name][0]), **b[name][1])}
-                new.append(key)
+                put(key, {"verdict": "new", "tree": dict(instructions=len(b[name][0]), **b[name][1])})
             else:
-                res[key] = {"verdict": "gone", "parent": dict(instructions=len(a[name][0]), **a[name][1])}
-                gone.append(key)
-    json.dump({"what": "device assembly (hipcc -S --cuda-device-only, gfx950, the library's flags) of %s in the "
-                       "parent commit and in this tree, compared per kernel instruction by instruction "
-                       "(directives, comments, labels and blank lines aside; branch targets by their number "
-                       "within the kernel)" % " and ".join(x + ".hip" for x in files),
-               "kernels": res, "library_kernels_rocprim_hipcub": lib,
-               "summary": {"same": same, "changed": changed, "new": new, "gone": gone}}, sys.stdout, indent=1)
+                put(key, {"verdict": "gone", "parent": dict(instructions=len(a[name][0]), **a[name][1])})
+    if unused:
+        raise SystemExit("no such pair of kernels (one only the parent has, one only the tree has): " +
+                         ", ".join("%s=%s" % p for p in sorted(unused)))
+    return {"what": "device assembly (hipcc -S --cuda-device-only, gfx950, the library's flags) of %s in the "
+                    "parent commit and in this tree, compared per kernel instruction by instruction "
+                    "(directives, comments, labels and blank lines aside; branch targets by their number "
+                    "within the kernel; 'A -> B': the parent's kernel A against the tree's B)"
+                    % " and ".join(x + ".hip" for x in files),
+            "kernels": res, "library_kernels_rocprim_hipcub": lib, "summary": summary}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("a_dir")
+    ap.add_argument("b_dir")
+    ap.add_argument("files", nargs="+", help="source names without extension: A/NAME.s against B/NAME.s")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW")
+    a = ap.parse_args()
+    pairs = []
+    for p in a.pair:
+        old, sep, new = p.partition("=")
+        if not (old and sep and new):
+            ap.error("--pair takes OLD=NEW")
+        pairs.append((old, new))
+    json.dump(compare(a.a_dir, a.b_dir, a.files, pairs), sys.stdout, indent=1)
     print()
 
 
