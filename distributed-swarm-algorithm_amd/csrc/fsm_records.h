@@ -100,4 +100,25 @@ int launch_physics_loop_sensed_field(int64_t n, const int32_t *ids, const uint2 
                                      const ObsFieldView &field, const LoopSense &ls, double dt, double max_speed,
                                      unsigned long long *singular, hipStream_t s);
 
+// Moving fields (contract O2; obstacle_field.hip).  A sensed entry point given a moving field's list:
+//   moving_field_fetch   before the call's entry wait: the current list queued to the host;
+//   moving_field_begin   after that wait, before anything is written: the call's grid and capacity
+//                        (SWARM_ERR_ARG / SWARM_ERR_RANGE: nothing written), the buffers, the entry list kept;
+//   moving_field_tick    per tick, before the physics kernel: the cell lists of the list as it stands, built on
+//                        the device with no host wait; *view reads them.  A tick whose pairs exceed the capacity
+//                        sets the field's error word and the stop word st[0] = 1 + k (the run is refused);
+//   moving_field_advance per tick, after the physics kernel: every obstacle advances once, unless st[0] is set;
+//   moving_field_restore_if_refused  (loops) the list back to its entry bits when st[0] is set;
+//   moving_field_error   the error word queued into *h_word (pinned) for the call's final wait, and
+//   moving_field_overflowed  its verdict: SWARM_ERR_RANGE with the error text.
+// find_moving_field: find_obstacle_field for a field that moves (NULL for a static one or a flat list).
+swarm_obstacle_field *find_moving_field(swarm_ctx *ctx, int64_t m, const double *obstacles);
+int moving_field_fetch(swarm_obstacle_field *f, hipStream_t s);
+int moving_field_begin(swarm_obstacle_field *f, int32_t ticks, double dt, bool keep_entry, hipStream_t s);
+int moving_field_tick(swarm_obstacle_field *f, unsigned long long *st, int32_t k, ObsFieldView *view, hipStream_t s);
+int moving_field_advance(swarm_obstacle_field *f, const unsigned long long *st, double dt, hipStream_t s);
+int moving_field_restore_if_refused(swarm_obstacle_field *f, const unsigned long long *st, hipStream_t s);
+int moving_field_error(swarm_obstacle_field *f, unsigned long long *h_word, hipStream_t s);
+int moving_field_overflowed();
+
 }  // namespace swarm

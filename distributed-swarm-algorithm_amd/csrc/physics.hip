@@ -867,6 +867,8 @@ int swarm_physics_step(swarm_ctx *ctx, int64_t n, const int32_t *ids, const uint
            "NULL agent array");
     SW_ARG(m == 0 || obstacles != nullptr, "obstacles is NULL");
     SW_ARG(pos_in != pos_out || n == 0, "pos_in and pos_out must differ (synchronous step)");
+    SW_ARG(!find_moving_field(ctx, m, obstacles),
+           "a moving obstacle field needs a sensed entry point (a fixed-graph step would read it as a frozen list)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n_singular) *n_singular = 0;
     if (n == 0) return SWARM_OK;
@@ -909,9 +911,14 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
     }
     // One grid for the whole call (loop_sense_begin).  Host wait 1 of 2; non-finite positions are refused here,
     // before anything is written.
+    // (contract O2) a moving field's list comes to the host with that wait; its grid and capacity are refused
+    // before anything is written as well
+    swarm_obstacle_field *mov = find_moving_field(ctx, m, obstacles);
     LoopSense ls{};
-    int rc = loop_sense_begin(ctx, n, pos, sense_radius, steps, dt, max_speed, &ls, s);
-    if (rc) return rc;
+    int rc;
+    if (mov && (rc = moving_field_fetch(mov, s))) return rc;
+    if ((rc = loop_sense_begin(ctx, n, pos, sense_radius, steps, dt, max_speed, &ls, s))) return rc;
+    if (mov && (rc = moving_field_begin(mov, steps, dt, false, s))) return rc;
     double2 *other;
     SW_ALLOC(other, ctx, S_SENSE_POS, size_t(n) * 16);
     unsigned long long *h = static_cast<unsigned long long *>(pinned(ctx, 64));
@@ -924,6 +931,17 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
         const double2 *pin = buf[k & 1];
         const int rc = loop_sense_tick(ctx, n, reinterpret_cast<const double *>(pin), k, &ls, s, false);
         if (rc) return rc;
+        if (mov) {  // the lists of O_{k}, the field's kernel on them, then every obstacle advances once
+            ObsFieldView view;
+            int rm;
+            if ((rm = moving_field_tick(mov, ls.st, k, &view, s))) return rm;
+            hipLaunchKernelGGL(k_physics_sensed_field, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids,
+                               state, leader_index, pin, buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel),
+                               reinterpret_cast<double2 *>(target), has_target, view, ls.g, ls.r2, ls.sorted, ls.off,
+                               ls.psort, dt, max_speed, ls.st);
+            SW_LAUNCHED();
+            return moving_field_advance(mov, ls.st, dt, s);
+        }
         if (fld)
             hipLaunchKernelGGL(k_physics_sensed_field, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, n, ids,
                                state, leader_index, pin, buf[(k + 1) & 1], reinterpret_cast<double2 *>(vel),
@@ -945,11 +963,14 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
         if ((rc = queue_step(queued))) break;
     if (queued & 1) SW_HIP(hipMemcpyAsync(pos, other, size_t(n) * 16, hipMemcpyDeviceToDevice, s));
     SW_HIP(hipMemcpyAsync(h, ls.st, 32, hipMemcpyDeviceToHost, s));
+    h[5] = 0;
+    if (mov) (void)moving_field_error(mov, h + 5, s);
     SW_HIP(hipStreamSynchronize(s));  // host wait 2 of 2
     const int32_t done = h[0] ? int32_t(h[0] - 1) : queued;
     if (steps_done) *steps_done = done;
     if (n_singular) *n_singular = int64_t(h[1]);
     if (rc) return rc;
+    if (h[5]) return moving_field_overflowed();
     if (h[0])
         return loop_sense_refusal(h, "agents too dense to sense at step %d (%d steps done)", int(done), int(done));
     return SWARM_OK;

@@ -1705,7 +1705,18 @@ int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t,
     const LoopArgs *loop = r.loop;
     // `obstacles` that is a live field's own list: the sensed loops take the field's path (contract O1)
     const swarm_obstacle_field *fld = r.sensed() ? find_obstacle_field(r.ctx, loop->m, loop->obstacles) : nullptr;
-    const int rc = fld        ? launch_physics_loop_sensed_field(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
+    if (fld && fld->moving) {  // contract O2: the lists of O_{t-1} built on the device, then every obstacle advances
+        swarm_obstacle_field *mov = find_moving_field(r.ctx, loop->m, loop->obstacles);
+        ObsFieldView view;
+        int rm;
+        if ((rm = moving_field_tick(mov, ls.st, int32_t(t - r.t0 - 1), &view, s))) return rm;
+        if ((rm = launch_physics_loop_sensed_field(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
+                                                   loop->has_target, view, ls, r.dt, loop->max_speed, sing, s)))
+            return rm;
+        if ((rm = moving_field_advance(mov, ls.st, r.dt, s))) return rm;
+    }
+    const int rc = fld && fld->moving ? SWARM_OK
+                   : fld        ? launch_physics_loop_sensed_field(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
                                                                  loop->has_target, obstacle_field_view(*fld), ls, r.dt,
                                                                  loop->max_speed, sing, s)
                    : r.sensed() ? launch_physics_loop_sensed(r.n, r.ids, f.rec, f.lrec, *lag, loop->vel, loop->target,
@@ -1728,7 +1739,7 @@ int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t,
 // run's one final host wait (none when nothing is asked for).  A refused tick (`snap` restores the caller's
 // arrays) withholds the counts and the singular count and sets refused_tick.
 int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap,
-              const TickSums &tasks, const TickSums &links, hipStream_t s) {
+              const TickSums &tasks, const TickSums &links, swarm_obstacle_field *mov, hipStream_t s) {
     const bool want_sing = r.loop && r.loop->n_singular;
     const bool want_tasks = r.tasked() && (r.task_counts || r.n_guard);
     const bool want_links = r.lossy() && r.link_counts;
@@ -1738,6 +1749,8 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
     }
     if (ls)
         if (const int rc = snap.restore_if_refused(ls->st, s)) return rc;
+    if (ls && mov)  // (contract O2) the list is the field's own array: back to its entry bits as well
+        if (const int rc = moving_field_restore_if_refused(mov, ls->st, s)) return rc;
     if (!(r.traffic || ls || want_sing || r.counts || want_tasks || want_links)) return SWARM_OK;
     // the sums that are asked for, one after the other from [16]: counts, task counts, link counts
     const size_t words = size_t(r.ticks) * 4, cnt_bytes = r.counts ? words * 8 : 0;
@@ -1750,6 +1763,8 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
     if (want_tasks && (rc = tasks.sum_into(ht, s))) return rc;
     if (r.traffic) SW_HIP(hipMemcpyAsync(h + 8, c.tr_sums, kTraffic * 8, hipMemcpyDeviceToHost, s));
     if (ls) SW_HIP(hipMemcpyAsync(h, ls->st, 32, hipMemcpyDeviceToHost, s));
+    h[5] = 0;
+    if (ls && mov && (rc = moving_field_error(mov, h + 5, s))) return rc;
     if (want_sing) SW_HIP(hipMemcpyAsync(h + 4, c.sing, 8, hipMemcpyDeviceToHost, s));
     if (r.counts && (rc = c.tick.sum_into(h + 16, s))) return rc;
     SW_HIP(hipStreamSynchronize(s));
@@ -1757,6 +1772,7 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
     if (ls && h[0]) {
         const int64_t tick = r.t0 + int64_t(h[0]);
         if (r.loop->refused_tick) *r.loop->refused_tick = tick;
+        if (h[5]) return moving_field_overflowed();
         return loop_sense_refusal(h, "agents too dense to sense at tick %lld (nothing of the call is kept)",
                                   static_cast<long long>(tick));
     }
@@ -1795,10 +1811,15 @@ int run_ticks(const TickRun &r) {
     // here; U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
     LoopSense ls{};
     EntrySnapshot snap;
+    // (contract O2) a moving field's list comes to the host with that wait; its grid and capacity are refused
+    // before anything is written, and the field keeps its entry list for a refused tick
+    swarm_obstacle_field *mov = sensed ? find_moving_field(r.ctx, loop->m, loop->obstacles) : nullptr;
     if (sensed) {
+        if (mov && (rc = moving_field_fetch(mov, s))) return rc;
         if ((rc = loop_sense_begin(r.ctx, r.n, loop->pos, loop->sense_radius, r.ticks, r.dt, loop->max_speed, &ls, s,
                                    radio ? loop->radio_radius : 0.0)))
             return rc;
+        if (mov && (rc = moving_field_begin(mov, r.ticks, r.dt, true, s))) return rc;
         if ((rc = snap.take(r, s))) return rc;
     }
     Counters cnt;
@@ -1849,7 +1870,7 @@ int run_ticks(const TickRun &r) {
     hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, r.fsm->state, r.fsm->alive,
                        r.fsm->has_leader_pos, r.fsm->leader, reinterpret_cast<float2 *>(r.fsm->leader_pos), f);
     SW_LAUNCHED();
-    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts.cnt, links, s);
+    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts.cnt, links, mov, s);
 }
 
 // The three loop entry points' own arguments (run_ticks checks the rest): U1 takes a sensor CSR and n < 2^31,
@@ -1911,6 +1932,8 @@ int check_channel(const swarm_channel *ch) {
 // A loop entry point: its checks, its outputs' resting values, the run.
 int run_loop(LoopKind kind, const TickRun &r) {
     if (const int rc = check_loop_args(kind, r.ctx, r.n, r.ticks, r.dt, *r.loop)) return rc;
+    SW_ARG(kind != kLoopCsr || !find_moving_field(r.ctx, r.loop->m, r.loop->obstacles),
+           "a moving obstacle field needs a sensed loop (a fixed-graph loop would read it as a frozen list)");
     if (r.loop->n_singular) *r.loop->n_singular = 0;
     if (r.loop->refused_tick) *r.loop->refused_tick = -1;
     return run_ticks(r);

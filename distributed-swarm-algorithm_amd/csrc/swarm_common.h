@@ -100,6 +100,24 @@ struct swarm_obstacle_field {
     swarm::Grid g{};
     std::vector<uint32_t> cell_off_host;
     std::vector<int32_t> idx_host;  // the cell lists as obstacle indices (swarm_obstacle_field_read)
+    // A moving field (contract O2; obstacle_field.hip): `obs` is the current list, in/out; the members
+    // above describe the creation list (or the last refresh).  The buffers below grow on demand, `obs` never moves.
+    int64_t live = 0;                 // the live obstacles of the list the host lists above describe
+    bool moving = false;
+    double *vel = nullptr;            // device: m x 2
+    double *entry = nullptr;          // device: the list as it was at a loop's entry (restored on a refused tick)
+    std::vector<double> vel_host;     // the velocities, checked finite (the call's box is planned from them)
+    std::vector<double> list_host;    // the list as fetched at a call's entry
+    swarm::Grid call_g{};             // the call's grid
+    int64_t capacity = 0;             // pairs the call's buffers hold (obstacle_motion.h, obs_pair_capacity)
+    unsigned long long *start = nullptr;  // device: m + 1 pair counts, then their exclusive sums
+    uint32_t *keys[2] = {};           // device: the pairs' cell keys, emitted and sorted
+    int32_t *vals[2] = {};            // device: the pairs' obstacle indices, emitted and sorted
+    uint32_t *dyn_off = nullptr;      // device: the tick's cell offsets
+    double *dyn_tri = nullptr;        // device: the tick's lists as packed triples
+    void *cub_tmp = nullptr;          // device: hipCUB's temporary storage
+    unsigned long long *err = nullptr;  // device: [0] set when a tick's pairs exceeded the capacity
+    size_t cap_pairs = 0, cap_cells = 0, cap_tmp = 0;  // what the buffers above hold
 };
 
 struct swarm_ctx {

@@ -40,7 +40,9 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_frontier_set_compact_escaped", "swarm_physics_run_sensed", "swarm_update_loop",
            "swarm_update_loop_sensed", "swarm_update_loop_radio", "swarm_update_loop_tasks",
            "swarm_obstacle_field_create", "swarm_obstacle_field_obstacles", "swarm_obstacle_field_read",
-           "swarm_obstacle_field_destroy", "swarm_update_loop_channel", "swarm_link_dropped")
+           "swarm_obstacle_field_destroy", "swarm_update_loop_channel", "swarm_link_dropped",
+           "swarm_obstacle_field_create_moving", "swarm_obstacle_field_set_velocities",
+           "swarm_obstacle_field_refresh")
 
 
 class SwarmError(RuntimeError):
@@ -212,6 +214,10 @@ def load(path: str = LIB_PATH):
         L.swarm_obstacle_field_obstacles.argtypes = [P, ctypes.POINTER(P)]
         L.swarm_obstacle_field_read.argtypes = [P, P, P]
         L.swarm_obstacle_field_destroy.argtypes = [P, P]
+        L.swarm_obstacle_field_create_moving.argtypes = [P, i64, P, P, ctypes.POINTER(P),
+                                                         ctypes.POINTER(ObstacleFieldInfo), P]
+        L.swarm_obstacle_field_set_velocities.argtypes = [P, P, P, P]
+        L.swarm_obstacle_field_refresh.argtypes = [P, P, ctypes.POINTER(ObstacleFieldInfo), P]
         for name in EXPORTS:
             if name not in ("swarm_last_error", "swarm_version"):
                 getattr(L, name).restype = ctypes.c_int
@@ -313,6 +319,16 @@ def ptr(t, dtype=None, numel=None, name="tensor"):
     if numel is not None and t.numel() < numel:
         raise ValueError(f"{name}: needs >= {numel} elements, has {t.numel()}")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def copy_to_host(out, dev_ptr):
+    """out (a contiguous numpy array) <- the device memory at dev_ptr, through the HIP runtime libswarm.so is
+    linked against (a blocking copy; the caller has waited for the stream that wrote the memory)."""
+    f = lib().hipMemcpy
+    f.argtypes, f.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int], ctypes.c_int
+    rc = f(out.ctypes.data_as(ctypes.c_void_p), dev_ptr, out.nbytes, 2)  # hipMemcpyDeviceToHost
+    if rc != 0:
+        raise SwarmError(ERR_HIP, f"hipMemcpy device -> host failed ({rc})")
 
 
 def stream():

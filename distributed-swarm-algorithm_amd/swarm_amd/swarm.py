@@ -133,9 +133,14 @@ class ObstacleField:
     read-only.  Pass it wherever an `obstacles=` list goes: the sensed calls (physics_step with sense_radius,
     update_loop_sensed / _radio / _tasks) then visit only the obstacles in an agent's reach, the fixed-graph
     calls read its list -- every result bit-identical to the same call with the list.  The field belongs to
-    the calling thread's ctx of its device; from another thread the calls read it as the flat list."""
+    the calling thread's ctx of its device; from another thread the calls read it as the flat list.
 
-    def __init__(self, obstacles, device):
+    With `velocities` (m x 2; contract O2) the field moves: every tick of a sensed call reads the list
+    as it stands, then every obstacle advances by fl(v * dt).  The field owns the current list (positions()),
+    `obstacles` stays the creation list.  The fixed-graph calls (physics_step without sense_radius, update_loop)
+    and a ctx or device other than the field's own raise: they would read the list as a frozen one."""
+
+    def __init__(self, obstacles, device, velocities=None):
         import weakref
         dev = device if isinstance(device, torch.device) else _dev(device)
         # (always a copy: later writes to the caller's tensor must not reach the field)
@@ -144,13 +149,20 @@ class ObstacleField:
         self.obstacles = src.numpy().copy()
         self.obstacles.flags.writeable = False
         self.m, self.device = int(src.shape[0]), dev
+        self.moving = velocities is not None
         info, self._handle = _lib.ObstacleFieldInfo(), ctypes.c_void_p()
         with torch.cuda.device(dev):
             d_obs = src.to(dev)
             self._ctx = _lib.ctx()
-            _lib.check(_lib.lib().swarm_obstacle_field_create(
-                self._ctx, self.m, _lib.ptr(d_obs) if self.m else None, ctypes.byref(self._handle),
-                ctypes.byref(info), _lib.stream()))
+            if self.moving:
+                d_vel = self._velocities(velocities)
+                _lib.check(_lib.lib().swarm_obstacle_field_create_moving(
+                    self._ctx, self.m, _lib.ptr(d_obs) if self.m else None, _lib.ptr(d_vel) if self.m else None,
+                    ctypes.byref(self._handle), ctypes.byref(info), _lib.stream()))
+            else:
+                _lib.check(_lib.lib().swarm_obstacle_field_create(
+                    self._ctx, self.m, _lib.ptr(d_obs) if self.m else None, ctypes.byref(self._handle),
+                    ctypes.byref(info), _lib.stream()))
         self.info = {k: getattr(info, k) for k, _ in _lib.ObstacleFieldInfo._fields_}
         self._ptr = ctypes.c_void_p()
         _lib.check(_lib.lib().swarm_obstacle_field_obstacles(self._handle, ctypes.byref(self._ptr)))
@@ -174,6 +186,55 @@ class ObstacleField:
                                                         idx.ctypes.data_as(ctypes.c_void_p)))
         return off, idx
 
+    def _velocities(self, v):
+        """The (m, 2) float64 device tensor of a velocities argument; ValueError for another shape."""
+        a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+        if a.shape != (self.m, 2):
+            raise ValueError(f"velocities must have shape ({self.m}, 2), got {a.shape}")
+        return torch.tensor(a).to(self.device).contiguous()
+
+    def _own_ctx(self):
+        """The field's ctx, which must be the calling thread's ctx of the field's device."""
+        self._check_open()
+        with torch.cuda.device(self.device):
+            if _lib.ctx() is not self._ctx:
+                raise ValueError("a moving obstacle field can only be used from the thread (ctx) that made it")
+        return self._ctx
+
+    def positions(self) -> np.ndarray:
+        """The current (m, 3) list: the creation list of a static field, where the ticks so far have carried
+        the obstacles of a moving one."""
+        self._check_open()
+        if not self.moving or self.m == 0:
+            return self.obstacles.copy()
+        out = np.empty((self.m, 3), np.float64)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            _lib.copy_to_host(out, self._ptr)
+        return out
+
+    def set_velocities(self, velocities):
+        """New velocities (m x 2) from the next tick on (swarm_obstacle_field_set_velocities)."""
+        self._check_open()
+        if not self.moving:
+            raise ValueError("the obstacle field does not move: make it with velocities")
+        d_vel = self._velocities(velocities)
+        ctx = self._own_ctx()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().swarm_obstacle_field_set_velocities(
+                ctx, self._handle, _lib.ptr(d_vel) if self.m else None, _lib.stream()))
+
+    def refresh(self):
+        """The cell lists of the current list, rebuilt by the device builder on the grid a static field of that
+        list would get (swarm_obstacle_field_refresh); updates `info`, and read() returns those lists."""
+        self._check_open()
+        info = _lib.ObstacleFieldInfo()
+        ctx = self._own_ctx() if self.moving else self._ctx
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().swarm_obstacle_field_refresh(ctx, self._handle, ctypes.byref(info), _lib.stream()))
+        self.info = {k: getattr(info, k) for k, _ in _lib.ObstacleFieldInfo._fields_}
+        return self.info
+
     def close(self):
         """Frees the field (waits for the device first).  Using it afterwards raises ValueError."""
         if not self.closed:
@@ -185,6 +246,8 @@ class ObstacleField:
         self._check_open()
         if dev != self.device:
             raise ValueError(f"the obstacle field lives on {self.device}, the swarm on {dev}")
+        if self.moving:
+            self._own_ctx()
         return self.m, self._ptr
 
 
@@ -195,6 +258,12 @@ def _channel(loss, loss_seed):
     if not 0.0 <= loss <= 1.0:  # (NaN fails both comparisons)
         raise ValueError(f"loss must be in [0, 1], got {loss}")
     return (loss, int(loss_seed) & 0xFFFFFFFFFFFFFFFF) if loss > 0.0 else None
+
+
+def _no_moving_field(obstacles, what):
+    """The fixed-graph calls refuse a moving field: they would read its list as a frozen one (contract O2)."""
+    if isinstance(obstacles, ObstacleField) and obstacles.moving:
+        raise ValueError(f"{what} cannot take a moving obstacle field: use a sensed call")
 
 
 def _obstacle_args(obstacles, dev):
@@ -640,12 +709,16 @@ class Swarm:
             cand = torch.where(ok, idx[leader.clamp(0, idx.numel() - 1).long()], out)
         return torch.where(self.state == _lib.FOLLOWER, cand, out).contiguous()
 
-    def obstacle_field(self, obstacles) -> ObstacleField:
+    def obstacle_field(self, obstacles, velocities=None) -> ObstacleField:
         """An ObstacleField of the (m, 3) [x, y, r] list on this swarm's device (contract O1, DESIGN 4j;
         swarm_obstacle_field_create).  The list is copied.  Built on the host, once; every `obstacles=`
         parameter accepts the field.  SwarmError: ERR_ARG for a non-finite entry or footprints without a finite
-        extent, ERR_RANGE for more than 2^26 (cell, obstacle) pairs."""
-        return ObstacleField(obstacles, self.device)
+        extent, ERR_RANGE for more than 2^26 (cell, obstacle) pairs.
+        velocities: (m, 2) makes it a moving field (contract O2; swarm_obstacle_field_create_moving):
+        the sensed calls rebuild its lists on the device every tick and advance every obstacle by v * dt after
+        the tick's physics; ERR_ARG for a non-finite velocity, ERR_RANGE when the pair bound from the radii
+        exceeds 2^26.  See ObstacleField."""
+        return ObstacleField(obstacles, self.device, velocities)
 
     def physics_step(self, obstacles=None, *, sensors=None, leader_index=None, dt: float = 0.1,
                      max_speed: float = 5.0, steps: int = 1, sense_radius: float | None = None) -> dict:
@@ -661,6 +734,8 @@ class Swarm:
         self.last_steps_done."""
         if sense_radius is not None and sensors is not None:
             raise ValueError("sense_radius senses the neighbours itself: sensors must be None")
+        if sense_radius is None:
+            _no_moving_field(obstacles, "physics_step without sense_radius")
         dev, n = self.device, self.n
         if not hasattr(self, "vel"):
             self.vel = torch.zeros((n, 2), dtype=torch.float64, device=dev)
@@ -850,6 +925,7 @@ class Swarm:
         Returns {"counts": (ticks x 4) as protocol_run, "singular": zero distances over all ticks} and,
         with trace_every = k > 0, "trace": (ticks // k, n, 2) positions after every k-th tick of the call,
         storage order.  update_loop_sensed senses the separation neighbours anew every tick instead."""
+        _no_moving_field(obstacles, "update_loop")
         return self._update_loop(ticks, None, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed, max_speed,
                                  mode, pull_frac, trace_every)
 

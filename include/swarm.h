@@ -842,6 +842,60 @@ int swarm_obstacle_field_obstacles(const swarm_obstacle_field *field, const doub
 int swarm_obstacle_field_read(const swarm_obstacle_field *field, uint32_t *cell_off_host, int32_t *idx_host);
 int swarm_obstacle_field_destroy(swarm_ctx *ctx, swarm_obstacle_field *field);
 
+/*
+ * Moving obstacles (contract O2): fields rebuilt on the device every tick.
+ * A moving field is a field (O1) whose list has one velocity (vx, vy) per obstacle; radii do not change.  The
+ * field owns the current list O (m x 3 f64; its device pointer is still the field's key and never changes) and
+ * the velocities (m x 2 f64).  For every sensed entry point given the field's pointer and m, with dt the call's
+ * own dt:
+ *   Reading.    The physics of tick t (step k) reads the agents' snapshot P_{t-1} and the list as it stands
+ *               then, O_{t-1}.
+ *   Advancing.  After that physics every obstacle advances once: x <- fl(x + fl(vx * dt)), y likewise; the
+ *               product and the sum are rounded separately, r is untouched.  Live and dead (r <= -5) alike.
+ *   In/out.     The list is in/out like pos: a run cut into chunks is the same run, and velocities may be
+ *               changed between calls.
+ *   Equivalence.  Every caller array, count, n_singular and the list itself after `ticks` ticks are
+ *               bit-identical to `ticks` repetitions of: the same entry point with ticks = 1 and the current
+ *               list as a flat list; then the advance above done by the caller.  (A moving field's tick is an
+ *               O1 field of O_{t-1}, and O1 gives the flat list's bits on any grid.)
+ *   Refusals.   A refused, too-dense tick of a loop (SWARM_ERR_RANGE, all or nothing) leaves the list as it was
+ *               at entry, like every other array.  A refused swarm_physics_run_sensed step leaves it advanced
+ *               exactly steps_done times, as pos is.  (A call with n == 0 or ticks == 0 runs no tick and
+ *               advances nothing.)
+ * The moving path is taken by swarm_physics_run_sensed, swarm_update_loop_sensed, _radio, _tasks and _channel.
+ * swarm_physics_step and swarm_update_loop (fixed graphs) given a moving field's pointer return SWARM_ERR_ARG
+ * with nothing written (they would read it as a frozen list); a static field there stays as it was.
+ *
+ * Per tick the cell lists are built on the call's stream with no host wait: per obstacle the live test, the
+ * half side and the footprint's cell range (the static builder's arithmetic); an exclusive sum; the (cell,
+ * obstacle) pairs written in ascending obstacle index; a stable radix sort by cell; the offsets by search; the
+ * triples gathered from the current list -- no atomics, every cell's list ascending, the static builder's lists.
+ * The grid is chosen once per call on the host, over the live footprints at entry and wherever the velocities
+ * put them in `ticks` advances (the list is copied to the host within the call's existing entry wait); results
+ * never depend on it.  The pair buffers are sized by a bound from the radii and the grid alone (per axis at most
+ * min(nc, floor(2 h / cell) + 3) cells, h = (5 + r)(1 + 1e-9); csrc/obstacle_motion.h has the proof).
+ * SWARM_ERR_ARG, nothing written: footprints whose box over the call has no finite extent.  SWARM_ERR_RANGE,
+ * nothing written: a bound above 2^26 pairs, or a grid of more than 2^31 cells -- at create_moving on the
+ * creation grid, at every call on the call's grid.  The device never writes past the capacity: a tick whose
+ * pairs exceeded it would refuse the run at that tick (SWARM_ERR_RANGE), as a too-dense tick does.
+ *
+ * swarm_obstacle_field_create_moving: swarm_obstacle_field_create plus velocities (device, m x 2 f64; NULL: all
+ * zero).  SWARM_ERR_ARG: a non-finite velocity, and whatever the static create refuses.
+ * swarm_obstacle_field_obstacles returns the pointer of the current list: reading it after a call is how the
+ * positions come back.
+ * swarm_obstacle_field_set_velocities (waits for the stream): SWARM_ERR_ARG on a static field or a non-finite
+ * entry, nothing changed.
+ * swarm_obstacle_field_refresh (for tests and tools; waits): rebuilds the cell lists with the device builder for
+ * the list as it stands, on the grid swarm_obstacle_field_create would choose for that list, and fills *info;
+ * swarm_obstacle_field_read then returns those lists.  On a static field it only fills *info.
+ */
+int swarm_obstacle_field_create_moving(swarm_ctx *ctx, int64_t m, const double *obstacles, const double *velocities,
+                                       swarm_obstacle_field **out, swarm_obstacle_field_info *info, void *stream);
+int swarm_obstacle_field_set_velocities(swarm_ctx *ctx, swarm_obstacle_field *field, const double *velocities,
+                                        void *stream);
+int swarm_obstacle_field_refresh(swarm_ctx *ctx, swarm_obstacle_field *field, swarm_obstacle_field_info *info,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
