@@ -147,8 +147,10 @@ int swarm_ctx_create(swarm_ctx **out) {
 
 int swarm_ctx_destroy(swarm_ctx *ctx) {
     if (!ctx) return SWARM_OK;
-    if (!ctx->fields.empty()) (void)hipDeviceSynchronize();  // a field may still be read by queued work
+    if (!ctx->fields.empty() || !ctx->boards.empty())
+        (void)hipDeviceSynchronize();  // a field or a board may still be read by queued work
     for (swarm_obstacle_field *f : ctx->fields) swarm::free_obstacle_field(f);
+    for (swarm_board *b : ctx->boards) swarm::free_board(b);
     for (int s = 0; s < swarm::S_NUM; ++s)
         if (ctx->slot[s]) (void)hipFree(ctx->slot[s]);
     if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);

@@ -49,6 +49,8 @@
 // templates on the channel (link_loss.h), k_*<NoLoss> what the loss-free loops launch, k_*<Lossy> what it adds.
 // The four tick kernels (k_tick_pull, k_tick, k_tick_radio, k_tick_radio_tasks) differ in how an agent receives;
 // what follows the receive is one function (settle_agent), and the two window kernels share the receive too.
+// swarm_update_loop_board (U1-B) is U1-T / U1-L on a board of up to 2^24 tasks with sparse per-agent state:
+// k_radio_outbox<true>, k_board_conflicts and k_tick_radio_board (BoardState), the same receive and settle_agent.
 // The host loop of every entry point is run_ticks, a sequence of stages that each own their scratch:
 // check_run_args, Counters (TickSums: a run's per-tick counters, also the task and link counts), pack_records,
 // PushState / RadioState / TaskState / launch_tick_pull (the receive launch by mode), EntrySnapshot (sensed),
@@ -58,6 +60,7 @@
 
 #include "fsm_records.h"
 #include "link_loss.h"
+#include "task_grid.h"
 #include "tick_segments.h"
 #include "utility.h"
 #include "window_merge.h"
@@ -1317,6 +1320,379 @@ __global__ __launch_bounds__(kBlock, 4) void k_tick_radio_tasks(int64_t n, int64
     if constexpr (Ch::kLossy) add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
 }
 
+// ---------------------------------------------------------------- board update loop (contract U1-B)
+// U1-T on a board of up to 2^24 tasks, DESIGN 4m: the same three launches per tick, the per-agent task state in
+// sparse rows in global memory instead of bit words and dense tables.  A row is ascending by task with its
+// empty slots (-1) behind the last entry, so it has one form whatever order its entries arrived in; a thread
+// searches and inserts in its own rows in place and only reads the rows of the senders it hears.
+//   status        Ks slots, task << 2 | code (OPEN is never stored);
+//   table         Kt slots in three arrays, task / winner / f32 utility;
+//   claim / conflict rows by tick parity, Ks / Kt slots of task indices -- written on demand like U1-T's words: a
+//                 row is touched only when it, or the row of two ticks ago in the same slot, holds something.
+// The board itself is a cell grid over the tasks (task_grid.h): an agent evaluates the tasks of the 3 x 3 task
+// cells around it -- three runs of the cell-sorted copy, a row of three cells is contiguous -- against the same
+// far pre-test, utility() and guard_flag() as k_tick_radio_tasks; an agent whose three runs are empty reads
+// nothing of its status row.  An agent that needs one slot more than a row has sets the call's verdict words
+// (st[0] = 1 + tick as a too-dense tick does, st[1] = kind << 32 | agent) and skips the insert: no thread writes
+// past a row, every later kernel of the call returns at once, and the caller's arrays are restored.
+constexpr int kRowLinear = 4;  // rows of at most this many entries are scanned, longer ones bisected
+
+struct BoardGrid {
+    const uint32_t *off;  // ncx * ncy + 1
+    const double2 *sxy;   // the tasks' positions in cell-sorted order
+    const int2 *sir;      // (task index, treq) in the same order
+    double xmin, ymin, xmax, ymax, inv_cell;
+    int64_t ncx, ncy;
+};
+
+struct BoardTick {
+    int32_t Ks, Kt;
+    int32_t k;  // the tick of the call, from 0 (the verdict word's)
+    const double2 *tpos;  // by task index: the claim handler's
+    const int8_t *treq;
+    BoardGrid tg;
+    const uint32_t *caps;
+    int32_t *status;
+    int32_t *tab_task, *tab_winner;
+    float *tab_util;
+    const int32_t *claim_in, *conflict_in;  // tick t-1's rows
+    int32_t *claim_out, *conflict_out;      // tick t's
+    uint8_t *cell_claim, *cell_conf;        // as TaskTick's
+    unsigned long long *cnt;
+    const uint8_t *sb_in;  // the sender bytes, as TaskTick's
+    uint8_t *sb_out;
+    unsigned long long *st;  // the call's verdict words
+};
+
+// How many of a row's K slots are taken (the first empty one).
+__device__ __forceinline__ int row_count(const int32_t *row, int K) {
+    int lo = 0, hi = K;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] >= 0) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The first of a row's cnt entries whose task (entry >> sh) is not below `task`; cnt when there is none.
+__device__ __forceinline__ int row_lower(const int32_t *row, int cnt, int32_t task, int sh) {
+    if (cnt <= kRowLinear) {
+        int q = 0;
+        while (q < cnt && (row[q] >> sh) < task) ++q;
+        return q;
+    }
+    int lo = 0, hi = cnt;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((row[mid] >> sh) < task) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <class V>
+__device__ __forceinline__ void row_open(V *row, int cnt, int at) {  // entries [at, cnt) one slot up
+    for (int m = cnt; m > at; --m) row[m] = row[m - 1];
+}
+
+// `task` into a row of task indices kept as a set (the claim and conflict rows; cnt < K by construction, and
+// never a write past the row).
+__device__ __forceinline__ void row_set_insert(int32_t *row, int K, int &cnt, int32_t task) {
+    const int q = row_lower(row, cnt, task, 0);
+    if ((q < cnt && row[q] == task) || cnt >= K) return;
+    row_open(row, cnt, q);
+    row[q] = task;
+    ++cnt;
+}
+
+// A status row's entry for `task` set to `code`, inserted when the task was OPEN; false: the row is full.
+__device__ __forceinline__ bool status_upsert(int32_t *row, int K, int &cnt, int32_t task, int32_t code) {
+    const int q = row_lower(row, cnt, task, 2);
+    const int32_t e = (task << 2) | code;
+    if (q < cnt && (row[q] >> 2) == task) {
+        if (row[q] != e) row[q] = e;
+        return true;
+    }
+    if (cnt >= K) return false;
+    row_open(row, cnt, q);
+    row[q] = e;
+    ++cnt;
+    return true;
+}
+
+__device__ __forceinline__ void row_clear(int32_t *row, int K) {
+    for (int q = 0; q < K && row[q] >= 0; ++q) row[q] = -1;
+}
+
+// (every overflowing thread of a tick stores the same st[0]; st[1] is one 64-bit store, any of them may stay)
+__device__ __forceinline__ void board_overflow(unsigned long long *st, int32_t k, int kind, int64_t agent) {
+    st[1] = (static_cast<unsigned long long>(kind) << 32) | static_cast<unsigned long long>(uint32_t(agent));
+    st[0] = 1ull + unsigned(k);
+}
+
+// The entry check of one sparse array of `total` slots in rows of K: every slot -1 or a task in [0, T) (with a
+// code in 1..3 where sh == 2), every row strictly ascending with the empties last.  bad[0] != 0: it is not.
+__global__ __launch_bounds__(kBlock) void k_board_check_rows(int64_t total, int K, int sh, int32_t T,
+                                                            const int32_t *__restrict__ a,
+                                                            unsigned long long *__restrict__ bad) {
+    bool wrong = false;
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < total; q += int64_t(gridDim.x) * kBlock) {
+        const int32_t e = a[q];
+        if (e == -1) continue;
+        if (e < 0 || (e >> sh) >= T || (sh && (e & 3) == 0)) {
+            wrong = true;
+        } else if (q % K) {
+            const int32_t prev = a[q - 1];
+            wrong |= prev < 0 || (prev >> sh) >= (e >> sh);
+        }
+    }
+    if (wrong) bad[0] = 1;
+}
+
+// The sender bytes of both parities from the caller's outbox and rows (once per call): a row holds something
+// iff its first slot does.
+__global__ __launch_bounds__(kBlock) void k_board_sender_bytes(int64_t n2, const uint8_t *__restrict__ ob,
+                                                              const int32_t *__restrict__ claim, int Ks,
+                                                              const int32_t *__restrict__ conflict, int Kt,
+                                                              uint8_t *__restrict__ sb) {
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < n2; q += int64_t(gridDim.x) * kBlock)
+        sb[q] = uint8_t((ob[q] & (kAcclaim | kHeartbeat)) | (claim[q * Ks] >= 0 ? kClaim : 0) |
+                        (conflict[q * Kt] >= 0 ? kConflict : 0));
+}
+
+// k_task_conflicts' walk over sparse rows: for every task of a heard sender's conflict row the winner is looked
+// up in the sender's table row (no entry: -1, everyone LOCKED) and the receiver's status row upserted; the last
+// conflict in walk order decides.  No thread of this launch writes a table or a conflict row.
+template <class Ch>
+__global__ __launch_bounds__(kBlock) void k_board_conflicts(int64_t n, int64_t t, const int32_t *__restrict__ ids,
+                                                           const uint2 *__restrict__ rec, Radio w, BoardTick k,
+                                                           Ch ch) {
+    if (w.st[0] != 0) return;
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const double2 p = w.psort[q0];
+        const int64_t cx = cell_coord(p.x, w.g.xmin, w.g.inv_cell, w.g.ncx);
+        const int64_t cy = cell_coord(p.y, w.g.ymin, w.g.inv_cell, w.g.ncy);
+        uint8_t any = 0;  // the nine bytes loaded at once
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const WindowCell wc = window_cell(w.g, cx, cy, c);
+            const uint8_t fl = k.cell_conf[wc.at];
+            any |= wc.in ? fl : uint8_t(0);
+        }
+        if (!any) continue;
+        const int64_t i = w.sorted[q0];
+        if (!fw_alive(rec[i].x)) continue;
+        const int32_t me = ids[i];
+        int32_t *srow = k.status + i * k.Ks;
+        int ns = -1;  // the status row's entries, counted when the first conflict arrives
+        bool over = false;
+        window_merge(p.x, p.y, w.g, w.sorted, w.off, [&](int32_t j, uint32_t q) {
+            if (!(w.ob_sorted[q] & kConflict) || j == int32_t(i)) return;
+            const double2 s = w.psort[q];
+            const double ex = p.x - s.x, ey = p.y - s.y;
+            if (!(ex * ex + ey * ey <= w.r2)) return;
+            if constexpr (Ch::kLossy)
+                if (ch.dropped(t, ids[j], me)) return;
+            const int32_t *crow = k.conflict_in + int64_t(j) * k.Kt;
+            const int32_t *tt = k.tab_task + int64_t(j) * k.Kt;
+            const int32_t *tw = k.tab_winner + int64_t(j) * k.Kt;
+            if (crow[0] < 0) return;
+            const int nt = row_count(tt, k.Kt);
+            if (ns < 0) ns = row_count(srow, k.Ks);
+            for (int c = 0; c < k.Kt; ++c) {
+                const int32_t a = crow[c];
+                if (a < 0) break;
+                const int at = row_lower(tt, nt, a, 0);
+                const int32_t win = at < nt && tt[at] == a ? tw[at] : -1;
+                // ASSIGNED (3) for the winner, LOCKED (2) for everyone else
+                over |= !status_upsert(srow, k.Ks, ns, a, win == me ? 3 : 2);
+            }
+        });
+        if (over) board_overflow(k.st, k.k, SWARM_BOARD_STATUS, i);
+    }
+}
+
+// hear_claims over sparse rows: the claims of sender j's row against the receiver's sorted table row, the `>
+// held + 5.0` rule and the re-affirmation as there; the tasks it sends a conflict on go into its conflict row.
+struct BoardRx {
+    const double2 *lag;
+    int32_t *tt, *tw;  // the receiver's table row
+    float *tu;
+    int32_t *cfrow;    // its conflict row of this tick (cleared by the caller)
+    int nt, ncf;       // their entries; nt < 0: not counted yet
+    unsigned handled, sent;
+    bool over;
+};
+
+__device__ __forceinline__ void hear_claims_board(BoardRx &c, const BoardTick &k, int32_t j, int32_t sid) {
+    const int32_t *crow = k.claim_in + int64_t(j) * k.Ks;
+    if (crow[0] < 0) return;
+    const double2 a = c.lag[j];
+    const uint32_t cp = k.caps[j];
+    if (c.nt < 0) c.nt = row_count(c.tt, k.Kt);
+    for (int q = 0; q < k.Ks; ++q) {
+        const int32_t task = crow[q];
+        if (task < 0) break;
+        const double2 tp = k.tpos[task];
+        const float u = float(utility(a.x, a.y, cp, tp.x, tp.y, k.treq[task], kUScale));
+        ++c.handled;
+        const int at = row_lower(c.tt, c.nt, task, 0);
+        const bool have = at < c.nt && c.tt[at] == task;
+        const int32_t hw = have ? c.tw[at] : -1;
+        const float hu = have ? c.tu[at] : 0.f;
+        if (hw < 0 || double(u) > double(hu) + kHysteresis) {
+            if (!have) {
+                if (c.nt >= k.Kt) {
+                    c.over = true;
+                    continue;
+                }
+                row_open(c.tt, c.nt, at);
+                row_open(c.tw, c.nt, at);
+                row_open(c.tu, c.nt, at);
+                c.tt[at] = task;
+                ++c.nt;
+            }
+            c.tw[at] = sid;
+            c.tu[at] = u;
+        } else if (hw == sid) {
+            continue;
+        }  // else: re-affirm the held winner
+        ++c.sent;
+        row_set_insert(c.cfrow, k.Kt, c.ncf, task);
+    }
+}
+
+// k_tick_radio_tasks' agent on a board (see the header of this section).  Over a lossy channel the link is
+// judged before the sender's election packets and claims are handled.
+template <class Ch>
+__global__ __launch_bounds__(kBlock) void k_tick_radio_board(int64_t n, int64_t t, const int32_t *__restrict__ ids,
+                                                            const double2 *__restrict__ pos, Fsm f, Radio w,
+                                                            uint8_t *__restrict__ ob_out, double dt, double timeout,
+                                                            double jitter, uint64_t seed,
+                                                            unsigned long long *__restrict__ counts, BoardTick k,
+                                                            Ch ch) {
+    __shared__ unsigned s_cnt[4], s_tcnt[4], s_lcnt[Ch::kLossy ? 4 : 1];
+    if (w.st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    if (threadIdx.x < 4) {
+        s_cnt[threadIdx.x] = s_tcnt[threadIdx.x] = 0;
+        if constexpr (Ch::kLossy) s_lcnt[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    const double now = double(t) * dt;
+    TickCounts c;
+    unsigned c_claim = 0, c_guard = 0, links = 0, lost = 0;
+    BoardRx rx{pos, nullptr, nullptr, nullptr, nullptr, -1, 0, 0u, 0u, false};
+    for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
+        const double2 p = w.psort[q0];
+        const int64_t i = w.sorted[q0];
+        const uint2 r = f.rec[i];
+        const uint32_t fw = r.x;
+        const uint8_t old = k.sb_out[i];  // what this slot's rows hold (tick t-2's sends)
+        int32_t *clrow = k.claim_out + i * k.Ks, *cfrow = k.conflict_out + i * k.Kt;
+        if (old & kClaim) row_clear(clrow, k.Ks);
+        if (old & kConflict) row_clear(cfrow, k.Kt);
+        if (!fw_alive(fw)) {
+            ob_out[i] = 0;
+            if (old) k.sb_out[i] = 0;
+            continue;
+        }
+        const int32_t me = ids[i];
+        const uint8_t st0 = fw_state(fw);
+        const bool hb_tick = ((t + fw_phase(fw)) % 10) == 0;
+        uint32_t bits = fw_bits(fw);
+        int32_t y = int32_t(r.y);
+        Heard h{st0, 0, false, false, 0, -1};
+        // only a LEADER's walk looks at claims (k_tick_radio_tasks' header)
+        const bool lead0 = st0 == ST_L;
+        const uint8_t rel = uint8_t(kAcclaim | kHeartbeat | (lead0 ? kClaim : 0));
+        rx.tt = k.tab_task + i * k.Kt;
+        rx.tw = k.tab_winner + i * k.Kt;
+        rx.tu = k.tab_util + i * k.Kt;
+        rx.cfrow = cfrow;
+        rx.nt = -1;
+        rx.ncf = 0;
+        rx.over = false;
+        hear_window(
+            p, i, w, rel, ids,
+            [&](int64_t cell) { return uint8_t(w.cell_send[cell] | (lead0 ? k.cell_claim[cell] : uint8_t(0))); },
+            [&](uint8_t o, int32_t sid, int32_t j) {
+                if constexpr (Ch::kLossy) {
+                    // (a claim-only sender is no election link; it is dropped all the same)
+                    const bool drop = ch.dropped(t, sid, me);
+                    const unsigned el = (o & (kAcclaim | kHeartbeat)) != 0;
+                    links += el;
+                    lost += el & unsigned(drop);
+                    if (drop) return;
+                }
+                hear(h, o, sid, j, me, hb_tick);
+                if ((o & kClaim) && h.st == ST_L) hear_claims_board(rx, k, j, sid);
+            });
+        apply_heard(i, h, t, pos, f, bits, y);
+        const uint8_t ob = settle_agent(i, h, r, bits, y, t, now, timeout, jitter, seed, ids, f, c);
+        ob_out[i] = ob;
+        // _process_tasks (292-302): the tasks still OPEN after this tick's conflicts, at the tick's snapshot,
+        // of the three runs of task cells around the agent
+        int ncl = 0;
+        bool over_s = false;
+        const BoardGrid &tg = k.tg;
+        const bool outside = p.x < tg.xmin - kTaskOutside || p.x > tg.xmax + kTaskOutside ||
+                             p.y < tg.ymin - kTaskOutside || p.y > tg.ymax + kTaskOutside;
+        if (!outside) {
+            const int64_t tcx = cell_coord(p.x, tg.xmin, tg.inv_cell, tg.ncx);
+            const int64_t tcy = cell_coord(p.y, tg.ymin, tg.inv_cell, tg.ncy);
+            const int64_t x0 = tcx > 0 ? tcx - 1 : 0, x1 = tcx + 1 < tg.ncx ? tcx + 1 : tg.ncx - 1;
+            uint32_t rb[3], re[3];  // the offsets loaded at once
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const int64_t yy = tcy + d - 1;
+                const bool in = yy >= 0 && yy < tg.ncy;
+                const int64_t row0 = in ? yy * tg.ncx : 0;
+                const uint32_t b = tg.off[row0 + x0], e = tg.off[row0 + x1 + 1];
+                rb[d] = in ? b : 0u;
+                re[d] = in ? e : 0u;
+            }
+            int32_t *srow = k.status + i * k.Ks;
+            int ns = -1;  // the status row's entries, counted when the first task passes the pre-test
+            uint32_t cp = 0;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                for (uint32_t q = rb[d]; q < re[d]; ++q) {
+                    const double2 tp = tg.sxy[q];
+                    const double dx = p.x - tp.x, dy = p.y - tp.y;
+                    if (!(dx * dx + dy * dy <= kClaimFar2)) continue;
+                    const int2 ir = tg.sir[q];
+                    if (ns < 0) {
+                        ns = row_count(srow, k.Ks);
+                        cp = k.caps[i];
+                    }
+                    const int at = row_lower(srow, ns, ir.x, 2);
+                    if (at < ns && (srow[at] >> 2) == ir.x) continue;  // not OPEN
+                    const double U = utility(p.x, p.y, cp, tp.x, tp.y, ir.y, kUScale);
+                    c_guard += guard_flag(U, kClaimThr);
+                    if (!(U > kClaimThr)) continue;
+                    if (ns >= k.Ks) {
+                        over_s = true;
+                        continue;
+                    }
+                    row_open(srow, ns, at);
+                    srow[at] = (ir.x << 2) | 1;  // TENTATIVE
+                    ++ns;
+                    row_set_insert(clrow, k.Ks, ncl, ir.x);
+                    ++c_claim;
+                }
+            }
+        }
+        if (over_s) board_overflow(k.st, k.k, SWARM_BOARD_STATUS, i);
+        if (rx.over) board_overflow(k.st, k.k, SWARM_BOARD_TABLE, i);
+        const uint8_t sent = uint8_t(ob | (ncl ? kClaim : 0) | (rx.ncf ? kConflict : 0));
+        if (sent != old) k.sb_out[i] = sent;
+    }
+    add_counts(c.lead, c.wait, c.acc, c.hb, s_cnt, counts);
+    add_counts(c_claim, rx.handled, rx.sent, c_guard, s_tcnt, k.cnt);
+    if constexpr (Ch::kLossy) add_counts(links, lost, 0u, 0u, s_lcnt, ch.cnt);
+}
+
 // ---------------------------------------------------------------- the host loop, in stages
 // One run's arguments, as the entry points fill them (`loop`: swarm_update_loop*, each tick then followed
 // by its physics step; `pos` is not used then, the heartbeats read the lagged buffer).
@@ -1341,7 +1717,11 @@ struct TickRun {
     int64_t *task_counts = nullptr, *n_guard = nullptr;
     const swarm_channel *ch = nullptr;  // U1-L (loss > 0: swarm_update_loop_channel's lossy kernels)
     int64_t *link_counts = nullptr;
+    const swarm_board *board = nullptr;  // U1-B (T > 0: swarm_update_loop_board), with its state and overflow info
+    const swarm_board_state *bstate = nullptr;
+    swarm_board_overflow *overflow = nullptr;
     bool tasked() const { return tasks && tasks->T > 0; }
+    bool boarded() const { return board && board->T > 0; }
     bool lossy() const { return ch && ch->loss > 0.0; }
     bool sensed() const { return loop && loop->sense_radius > 0.0; }
     bool radio() const { return loop && loop->radio_radius > 0.0; }
@@ -1601,6 +1981,96 @@ struct TaskState {
     }
 };
 
+// Board mode (U1-B): TaskState's scratch and counters, the entry check of the caller's sparse rows and the
+// tick's three launches over them.
+struct BoardState {
+    TickSums cnt;
+    uint8_t *sb = nullptr;  // the sender bytes, 2n by tick parity (BoardTick)
+
+    // The entry check, queued before the call's entry wait (loop_sense_begin's): its verdict is on the host when
+    // that wait ends, before anything is written.
+    static int check_entry(const TickRun &r, hipStream_t s) {
+        const swarm_board &b = *r.board;
+        const swarm_board_state &q = *r.bstate;
+        const int64_t n = r.n;
+        SW_HIP(hipMemsetAsync(b.verdict, 0, 8, s));
+        const struct {
+            const int32_t *a;
+            int64_t rows;
+            int K, sh;
+        } arr[4] = {{q.status, n, q.Ks, 2}, {q.tab_task, n, q.Kt, 0}, {q.claim_out, 2 * n, q.Ks, 0},
+                    {q.conflict_out, 2 * n, q.Kt, 0}};
+        for (const auto &a : arr) {
+            hipLaunchKernelGGL(k_board_check_rows, dim3(grid_for(a.rows * a.K, kBlock, 8192)), dim3(kBlock), 0, s,
+                               a.rows * a.K, a.K, a.sh, int32_t(b.T), a.a, b.verdict);
+            SW_LAUNCHED();
+        }
+        b.verdict_host[0] = 1;  // (overwritten by the copy: a wait that never came reads as a refusal)
+        SW_HIP(hipMemcpyAsync(b.verdict_host, b.verdict, 8, hipMemcpyDeviceToHost, s));
+        return SWARM_OK;
+    }
+    static int entry_verdict(const TickRun &r) {
+        SW_ARG(r.board->verdict_host[0] == 0,
+               "a sparse task row holds an entry that is no task of the board, a status code outside 1..3, or is "
+               "not strictly ascending with its empty slots last");
+        return SWARM_OK;
+    }
+
+    int begin(const TickRun &r, hipStream_t s) {
+        const swarm_board_state &q = *r.bstate;
+        if (const int rc = cnt.begin(r, S_TASK_COUNTS, s)) return rc;
+        SW_ALLOC(sb, r.ctx, S_TASK_SENDERS, size_t(r.n) * 2);
+        hipLaunchKernelGGL(k_board_sender_bytes, dim3(grid_for(2 * r.n, kBlock, 8192)), dim3(kBlock), 0, s, 2 * r.n,
+                           r.fsm->outbox, q.claim_out, q.Ks, q.conflict_out, q.Kt, sb);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+
+    // rs: bound to the tick's binning; st: the call's verdict words; ch: NoLoss{}, or the tick's Lossy
+    template <class Ch>
+    int launch(const TickRun &r, const Fsm &f, const Tick &k, const RadioState &rs, unsigned long long *st, Ch ch,
+               hipStream_t s) const {
+        const dim3 grid(grid_for(r.n, kBlock, 8192));
+        const swarm_board &b = *r.board;
+        const swarm_board_state &q = *r.bstate;
+        const size_t un = size_t(r.n), in = size_t((k.t - 1) & 1) * un, out = size_t(k.t & 1) * un;
+        const size_t ks = size_t(q.Ks), kt = size_t(q.Kt);
+        const BoardTick bt{q.Ks,
+                           q.Kt,
+                           int32_t(k.t - r.t0 - 1),
+                           reinterpret_cast<const double2 *>(b.tpos),
+                           b.treq,
+                           BoardGrid{b.cell_off, reinterpret_cast<const double2 *>(b.sxy),
+                                     reinterpret_cast<const int2 *>(b.sir), b.g.xmin, b.g.ymin, b.g.xmax, b.g.ymax,
+                                     b.g.inv_cell, b.g.ncx, b.g.ncy},
+                           q.caps,
+                           q.status,
+                           q.tab_task,
+                           q.tab_winner,
+                           q.tab_util,
+                           q.claim_out + in * ks,
+                           q.conflict_out + in * kt,
+                           q.claim_out + out * ks,
+                           q.conflict_out + out * kt,
+                           rs.rw.cell_send + rs.cells,
+                           rs.rw.cell_send + 2 * rs.cells,
+                           cnt.at(k.t),
+                           sb + in,
+                           sb + out,
+                           st};
+        SW_HIP(hipMemsetAsync(rs.rw.cell_send, 0, 3 * rs.cells, s));
+        hipLaunchKernelGGL(k_radio_outbox<true>, grid, dim3(kBlock), 0, s, r.n, bt.sb_in, rs.rw, bt.cell_claim,
+                           bt.cell_conf);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_board_conflicts<Ch>, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec, rs.rw, bt, ch);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_tick_radio_board<Ch>, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
+                           k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, bt, ch);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+};
+
 int launch_tick_pull(const TickRun &r, unsigned grid, const Fsm &f, const Tick &k, hipStream_t s) {
     hipLaunchKernelGGL(k_tick_pull, dim3(grid), dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, r.row_ptr, r.col, f,
                        k.ob_in, k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt);
@@ -1635,6 +2105,13 @@ struct EntrySnapshot {
             const size_t row = un * size_t(b.T) * 4;
             const Kept more[6] = {{b.status_lo, un * 8, 0},     {b.status_hi, un * 8, 0}, {b.claim_out, un * 16, 0},
                                   {b.conflict_out, un * 16, 0}, {b.tab_winner, row, 0},   {b.tab_util, row, 0}};
+            for (int q = 0; q < 6; ++q) kept[nkept++] = more[q];
+        }
+        if (r.boarded()) {  // U1-B: the six sparse arrays
+            const swarm_board_state &b = *r.bstate;
+            const size_t srow = un * size_t(b.Ks) * 4, trow = un * size_t(b.Kt) * 4;
+            const Kept more[6] = {{b.status, srow, 0},     {b.tab_task, trow, 0},      {b.tab_winner, trow, 0},
+                                  {b.tab_util, trow, 0},   {b.claim_out, 2 * srow, 0}, {b.conflict_out, 2 * trow, 0}};
             for (int q = 0; q < 6; ++q) kept[nkept++] = more[q];
         }
         size_t total = 0;
@@ -1741,7 +2218,7 @@ int tick_physics(const TickRun &r, const Fsm &f, const LoopSense &ls, int64_t t,
 int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const EntrySnapshot &snap,
               const TickSums &tasks, const TickSums &links, swarm_obstacle_field *mov, hipStream_t s) {
     const bool want_sing = r.loop && r.loop->n_singular;
-    const bool want_tasks = r.tasked() && (r.task_counts || r.n_guard);
+    const bool want_tasks = (r.tasked() || r.boarded()) && (r.task_counts || r.n_guard);
     const bool want_links = r.lossy() && r.link_counts;
     if (r.traffic) {  // (pull-mode runs: every tick walks every row -- the receivers are all agents)
         hipLaunchKernelGGL(k_sum_traffic, dim3(1), dim3(kWave), 0, s, c.tr_shards, c.tr_sums);
@@ -1773,6 +2250,16 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
         const int64_t tick = r.t0 + int64_t(h[0]);
         if (r.loop->refused_tick) *r.loop->refused_tick = tick;
         if (h[5]) return moving_field_overflowed();
+        if (h[1]) {  // U1-B: a sparse row overflowed (st[1] = kind << 32 | agent)
+            const int kind = int(h[1] >> 32);
+            const long long agent = static_cast<long long>(h[1] & 0xFFFFFFFFull);
+            if (r.overflow) *r.overflow = swarm_board_overflow{kind, 0, agent};
+            set_error("agent %lld (storage index) needs more than its %d %s slots at tick %lld (nothing of the call "
+                      "is kept; repeat it with larger rows)",
+                      agent, kind == SWARM_BOARD_STATUS ? r.bstate->Ks : r.bstate->Kt,
+                      kind == SWARM_BOARD_STATUS ? "status" : "table", static_cast<long long>(tick));
+            return SWARM_ERR_RANGE;
+        }
         return loop_sense_refusal(h, "agents too dense to sense at tick %lld (nothing of the call is kept)",
                                   static_cast<long long>(tick));
     }
@@ -1806,7 +2293,7 @@ int run_ticks(const TickRun &r) {
     }
     hipStream_t s = static_cast<hipStream_t>(r.stream);
     const LoopArgs *loop = r.loop;
-    const bool sensed = r.sensed(), radio = r.radio(), push = r.push(), tasked = r.tasked();
+    const bool sensed = r.sensed(), radio = r.radio(), push = r.push(), tasked = r.tasked(), boarded = r.boarded();
     // U1-S / U1-R: the call's grid (the loop's one host wait before its end; non-finite positions are refused
     // here; U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
     LoopSense ls{};
@@ -1816,9 +2303,11 @@ int run_ticks(const TickRun &r) {
     swarm_obstacle_field *mov = sensed ? find_moving_field(r.ctx, loop->m, loop->obstacles) : nullptr;
     if (sensed) {
         if (mov && (rc = moving_field_fetch(mov, s))) return rc;
+        if (boarded && (rc = BoardState::check_entry(r, s))) return rc;
         if ((rc = loop_sense_begin(r.ctx, r.n, loop->pos, loop->sense_radius, r.ticks, r.dt, loop->max_speed, &ls, s,
                                    radio ? loop->radio_radius : 0.0)))
             return rc;
+        if (boarded && (rc = BoardState::entry_verdict(r))) return rc;
         if (mov && (rc = moving_field_begin(mov, r.ticks, r.dt, true, s))) return rc;
         if ((rc = snap.take(r, s))) return rc;
     }
@@ -1831,12 +2320,14 @@ int run_ticks(const TickRun &r) {
     PushState ps;
     RadioState rs;
     TaskState ts;
+    BoardState bs;
     TickSums links;  // a lossy run (U1-L): per tick the election links and those of them that were dropped
     TickClocks clk;
     if (push && (rc = ps.begin(r, grid, s))) return rc;
     if ((rc = clk.begin(r, ps, s))) return rc;
-    if (radio && (rc = rs.begin(r, ls, tasked ? 3 : 1))) return rc;
+    if (radio && (rc = rs.begin(r, ls, tasked || boarded ? 3 : 1))) return rc;
     if (tasked && (rc = ts.begin(r, s))) return rc;
+    if (boarded && (rc = bs.begin(r, s))) return rc;
     const bool lossy = radio && r.lossy();
     if (lossy && (rc = links.begin(r, S_LINK_COUNTS, s))) return rc;
     double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
@@ -1853,7 +2344,11 @@ int run_ticks(const TickRun &r) {
         // far beyond the agents: offsets by search)
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
         if (radio) rs.bind(ls);
-        auto window_tick = [&](auto ch) { return tasked ? ts.launch(r, f, k, rs, ch, s) : rs.launch(r, f, k, ch, s); };
+        auto window_tick = [&](auto ch) {
+            return boarded  ? bs.launch(r, f, k, rs, ls.st, ch, s)
+                   : tasked ? ts.launch(r, f, k, rs, ch, s)
+                            : rs.launch(r, f, k, ch, s);
+        };
         rc = lossy   ? window_tick(Lossy{r.ch->loss, r.ch->seed, links.at(t)})
              : radio ? window_tick(NoLoss{})
              : push  ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
@@ -1870,7 +2365,7 @@ int run_ticks(const TickRun &r) {
     hipLaunchKernelGGL(k_unpack_fsm, dim3(grid), dim3(kBlock), 0, s, r.n, r.fsm->state, r.fsm->alive,
                        r.fsm->has_leader_pos, r.fsm->leader, reinterpret_cast<float2 *>(r.fsm->leader_pos), f);
     SW_LAUNCHED();
-    return read_back(r, cnt, sensed ? &ls : nullptr, snap, ts.cnt, links, mov, s);
+    return read_back(r, cnt, sensed ? &ls : nullptr, snap, boarded ? bs.cnt : ts.cnt, links, mov, s);
 }
 
 // The three loop entry points' own arguments (run_ticks checks the rest): U1 takes a sensor CSR and n < 2^31,
@@ -1920,6 +2415,21 @@ int check_tasks(swarm_ctx *ctx, int64_t n, const swarm_tasks *b, void *stream) {
     SW_HIP(hipMemcpyAsync(rq, b->treq, size_t(b->T), hipMemcpyDeviceToHost, s));
     SW_HIP(hipStreamSynchronize(s));
     for (int k = 0; k < b->T; ++k) SW_ARG(!bad_req(rq[k]), "a treq outside [-1, 31]");
+    return SWARM_OK;
+}
+
+// swarm_update_loop_board's own arguments: the handle and the sparse state (T == 0: no array is looked at).  The
+// rows' contents are checked on the device (BoardState::check_entry).
+int check_board(swarm_ctx *ctx, int64_t n, const swarm_board *b, const swarm_board_state *q) {
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(b != nullptr, "board is NULL");
+    SW_ARG(q != nullptr, "state is NULL");
+    SW_ARG(q->Ks >= 1 && q->Ks <= 4096 && q->Kt >= 1 && q->Kt <= 4096, "status / table slots must be in [1, 4096]");
+    SW_ARG(live_board(ctx, b), "the board is not a live board of this ctx");
+    if (b->T == 0) return SWARM_OK;
+    SW_ARG(n <= 0 || (q->caps && q->status && q->tab_task && q->tab_winner && q->tab_util && q->claim_out &&
+                      q->conflict_out),
+           "NULL task array");
     return SWARM_OK;
 }
 
@@ -2041,6 +2551,30 @@ int swarm_update_loop_channel(swarm_ctx *ctx, int64_t n, const int32_t *ids, dou
     return run_loop(kLoopRadio, {ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
                                  timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream,
                                  tasks, task_counts, n_guard, ch, link_counts});
+}
+
+int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                            const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                            double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                            int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                            const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                            double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                            int64_t *refused_tick, const swarm_board *board, const swarm_board_state *state,
+                            int64_t *task_counts, int64_t *n_guard, void *stream, const swarm_channel *ch,
+                            int64_t *link_counts, swarm_board_overflow *overflow) {
+    using namespace swarm;
+    if (overflow) *overflow = swarm_board_overflow{SWARM_BOARD_FITS, 0, -1};
+    if (const int rc = check_channel(ch)) return rc;
+    if (const int rc = check_board(ctx, n, board, state)) return rc;
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
+                        trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
+    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream,
+              nullptr, task_counts, n_guard, ch, link_counts};
+    r.board = board;
+    r.bstate = state;
+    r.overflow = overflow;
+    return run_loop(kLoopRadio, r);
 }
 
 int swarm_link_dropped(uint64_t seed, int64_t t, int32_t sid, int32_t rid, double loss) {

@@ -120,8 +120,26 @@ struct swarm_obstacle_field {
     size_t cap_pairs = 0, cap_cells = 0, cap_tmp = 0;  // what the buffers above hold
 };
 
+// A task board (contract U1-B; task_board.hip builds it, protocol.hip reads it).  Everything it points to is
+// owned by the board until swarm_board_destroy (or its ctx's destroy).
+struct swarm_board {
+    int64_t T = 0;
+    double *tpos = nullptr;        // device: the caller's positions, T x 2 (by task index: the claim handler's)
+    int8_t *treq = nullptr;        // device: T
+    uint32_t *cell_off = nullptr;  // device: ncx * ncy + 1
+    double *sxy = nullptr;         // device: the tasks' positions in cell-sorted order, T x 2
+    int32_t *sir = nullptr;        // device: (task index, treq) in cell-sorted order, T x 2
+    unsigned long long *verdict = nullptr;       // device: the entry check's word
+    unsigned long long *verdict_host = nullptr;  // pinned: its copy, read after the call's entry wait
+    swarm::Grid g{};
+    int64_t longest = 0;
+    std::vector<uint32_t> cell_off_host;
+    std::vector<int32_t> idx_host;
+};
+
 struct swarm_ctx {
     std::vector<swarm_obstacle_field *> fields;  // the live obstacle fields created on this ctx
+    std::vector<swarm_board *> boards;           // the live task boards created on this ctx
     swarm::AucPersist auc;         // sharded auction between begin and the round calls
     int device = 0;
     void *slot[swarm::S_NUM] = {};
@@ -191,6 +209,13 @@ inline const swarm_obstacle_field *find_obstacle_field(const swarm_ctx *ctx, int
 }
 // Frees a field's memory (the caller has taken it off its ctx's list and made sure the device is done with it).
 void free_obstacle_field(swarm_obstacle_field *f);
+// The same for a task board (task_board.hip); live_board: `b` is a live board of ctx.
+void free_board(swarm_board *b);
+inline bool live_board(const swarm_ctx *ctx, const swarm_board *b) {
+    for (const swarm_board *q : ctx->boards)
+        if (q == b) return true;
+    return false;
+}
 
 }  // namespace swarm
 

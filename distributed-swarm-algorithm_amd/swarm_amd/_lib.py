@@ -42,7 +42,10 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_obstacle_field_create", "swarm_obstacle_field_obstacles", "swarm_obstacle_field_read",
            "swarm_obstacle_field_destroy", "swarm_update_loop_channel", "swarm_link_dropped",
            "swarm_obstacle_field_create_moving", "swarm_obstacle_field_set_velocities",
-           "swarm_obstacle_field_refresh")
+           "swarm_obstacle_field_refresh", "swarm_board_create", "swarm_board_info", "swarm_board_read",
+           "swarm_board_destroy", "swarm_update_loop_board")
+BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
+BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
 
 
 class SwarmError(RuntimeError):
@@ -66,6 +69,24 @@ class Tasks(ctypes.Structure):
 class Channel(ctypes.Structure):
     """swarm_channel: the lossy channel of swarm_update_loop_channel."""
     _fields_ = [("loss", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+class BoardDesc(ctypes.Structure):
+    """swarm_board_desc."""
+    _fields_ = [("T", ctypes.c_int64), ("ncx", ctypes.c_int64), ("ncy", ctypes.c_int64), ("cell", ctypes.c_double),
+                ("xmin", ctypes.c_double), ("ymin", ctypes.c_double), ("longest", ctypes.c_int64)]
+
+
+class BoardState(ctypes.Structure):
+    """swarm_board_state: every agent's sparse task state (device pointers)."""
+    _fields_ = [("Ks", ctypes.c_int32), ("Kt", ctypes.c_int32)] + \
+               [(k, ctypes.c_void_p) for k in ("caps", "status", "tab_task", "tab_winner", "tab_util", "claim_out",
+                                               "conflict_out")]
+
+
+class BoardOverflow(ctypes.Structure):
+    """swarm_board_overflow."""
+    _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("agent", ctypes.c_int64)]
 
 
 class ObstacleFieldInfo(ctypes.Structure):
@@ -218,6 +239,13 @@ def load(path: str = LIB_PATH):
                                                          ctypes.POINTER(ObstacleFieldInfo), P]
         L.swarm_obstacle_field_set_velocities.argtypes = [P, P, P, P]
         L.swarm_obstacle_field_refresh.argtypes = [P, P, ctypes.POINTER(ObstacleFieldInfo), P]
+        L.swarm_board_create.argtypes = [P, i64, P, P, ctypes.POINTER(P), ctypes.POINTER(BoardDesc), P]
+        L.swarm_board_info.argtypes = [P, ctypes.POINTER(BoardDesc)]
+        L.swarm_board_read.argtypes = [P, P, P]
+        L.swarm_board_destroy.argtypes = [P, P]
+        L.swarm_update_loop_board.argtypes = L.swarm_update_loop_radio.argtypes[:-1] + [
+            P, ctypes.POINTER(BoardState), P, ctypes.POINTER(i64), P, ctypes.POINTER(Channel), P,
+            ctypes.POINTER(BoardOverflow)]
         for name in EXPORTS:
             if name not in ("swarm_last_error", "swarm_version"):
                 getattr(L, name).restype = ctypes.c_int

@@ -127,6 +127,18 @@ def _destroy_field(ctx, handle):
     handle.value = None
 
 
+def _destroy_board(ctx, handle):
+    """A task board's finalizer (set_task_board), as _destroy_field."""
+    L = _lib._lib
+    if L is not None and handle.value and ctx.handle.value:
+        with torch.cuda.device(ctx.device):
+            L.swarm_board_destroy(ctx.handle, handle)
+    handle.value = None
+
+
+BOARD_OVERFLOW_KINDS = {_lib.BOARD_STATUS: "status", _lib.BOARD_TABLE: "table"}
+
+
 class ObstacleField:
     """An obstacle field (contract O1, swarm_obstacle_field): a list of m obstacles (x, y, r) with, per cell
     of a grid over them, the obstacles that can act on an agent there.  Made by Swarm.obstacle_field();
@@ -1065,11 +1077,146 @@ class Swarm:
             a.task_claims = {int(tid): {"winner": int(w[i, k]), "utility": float(u[i, k])}
                              for k, tid in enumerate(task_ids) if w[i, k] >= 0}
 
+    # ------------------------------------------------------------------ task loop on boards of any size (U1-B)
+    def set_task_board(self, tx, ty=None, treq=None, *, status_slots: int = 16, table_slots: int = 16):
+        """set_tasks for a board of up to 2^24 tasks (contract U1-B; swarm_board_create): every task OPEN at
+        every agent, every claim table empty, nothing in flight, the per-agent state sparse -- status_slots
+        non-OPEN statuses and table_slots claim-table entries per agent at most, each in [1, 4096].  An agent
+        that needs one more makes update_loop_board refuse the call (grow_board, then repeat it).  Arguments as
+        set_tasks, a tasks_from_dict result included; the positions and treq are checked here, by the library
+        (SwarmError ERR_ARG).  The 64-task board of set_tasks is a separate one and is left alone."""
+        import weakref
+        ids = None
+        if ty is None and isinstance(tx, tuple) and len(tx) == 4:
+            ids, tx, ty, treq = tx
+        tx = np.atleast_1d(np.asarray(tx, np.float64))
+        ty = np.atleast_1d(np.asarray(ty, np.float64))
+        if tx.ndim != 1 or tx.shape != ty.shape:
+            raise ValueError("tx and ty must be 1-D arrays of one length")
+        T, n, dev = int(tx.shape[0]), self.n, self.device
+        tq = np.full(T, -1, np.int8) if treq is None else np.atleast_1d(np.asarray(treq)).astype(np.int64)
+        if tq.shape != (T,):
+            raise ValueError(f"treq: expected {T} values, got shape {tuple(tq.shape)}")
+        if T and (int(tq.min()) < -128 or int(tq.max()) > 127):
+            raise ValueError("treq must fit a signed byte (the library accepts -1 .. 31)")
+        ks, kt = int(status_slots), int(table_slots)
+        for name, k in (("status_slots", ks), ("table_slots", kt)):
+            if not 1 <= k <= _lib.BOARD_MAX_SLOTS:
+                raise ValueError(f"{name} must be in [1, {_lib.BOARD_MAX_SLOTS}], got {k}")
+        old = getattr(self, "board", None)
+        if old is not None:
+            old["finalizer"]()
+        desc, handle = _lib.BoardDesc(), ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            tpos = torch.as_tensor(np.stack([tx, ty], 1), device=dev).contiguous()
+            rq = torch.as_tensor(tq.astype(np.int8), device=dev)
+            ctx = _lib.ctx()
+            _lib.check(_lib.lib().swarm_board_create(ctx, T, _lib.ptr(tpos) if T else None,
+                                                     _lib.ptr(rq) if T else None, ctypes.byref(handle),
+                                                     ctypes.byref(desc), _lib.stream()))
+        e = lambda rows, k: torch.full((rows, k), -1, dtype=torch.int32, device=dev)  # noqa: E731
+        self.board = dict(T=T, handle=handle, ctx=ctx, Ks=ks, Kt=kt,
+                          info={k: getattr(desc, k) for k, _ in _lib.BoardDesc._fields_},
+                          status=e(n, ks), tab_task=e(n, kt), tab_winner=e(n, kt),
+                          tab_util=torch.zeros((n, kt), dtype=torch.float32, device=dev),
+                          claim_out=e(2 * n, ks), conflict_out=e(2 * n, kt),
+                          finalizer=weakref.finalize(self, _destroy_board, ctx, handle))
+        self.board_task_ids = np.arange(T, dtype=np.int64) if ids is None else np.asarray(ids, np.int64)
+        self.last_board_overflow = None
+        return self
+
+    def update_loop_board(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
+                          kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
+                          max_speed: float = 5.0, trace_every: int = 0, loss: float = 0.0,
+                          loss_seed: int = 0) -> dict:
+        """update_loop_tasks on the board of set_task_board (contract U1-B; swarm_update_loop_board): the same
+        tick, handler for handler, the same keywords, lossy channel and obstacle fields included, and the same
+        dict.  An agent that needs more status or table slots than the board was set with makes the call all or
+        nothing, like a too-dense tick: SwarmError ERR_RANGE, self.last_refused_tick is the tick and
+        self.last_board_overflow (kind "status" or "table", one such agent in input order); grow_board() and the
+        same call then run it.  Sparse rows that are not canonical (set by hand) are refused with ERR_ARG."""
+        channel = _channel(loss, loss_seed)
+        if not hasattr(self, "board"):
+            raise RuntimeError("no task board: call set_task_board() first")
+        radio_radius, sense_radius = float(radio_radius), float(sense_radius)
+        for name, r in (("radio_radius", radio_radius), ("sense_radius", sense_radius)):
+            if not (r > 0.0 and np.isfinite(r)):
+                raise ValueError(f"{name} must be positive and finite, got {r}")
+        return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
+                                 max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius, board=self.board,
+                                 channel=channel)
+
+    def board_status(self) -> torch.Tensor:
+        """(n, status_slots) int32 sparse status rows, storage order: task << 2 | code (1 TENTATIVE, 2 LOCKED,
+        3 ASSIGNED) ascending by task, -1 behind the last entry."""
+        return self.board["status"]
+
+    def board_tables(self):
+        """Every agent's task_claims as sparse rows, storage order: (task (n, table_slots) int32 ascending, -1 =
+        empty; winner int32; utility float32)."""
+        b = self.board
+        return b["tab_task"], b["tab_winner"], b["tab_util"]
+
+    def board_dense(self):
+        """The board state as update_loop_tasks' dense arrays, for small n x T, storage order: (status (n, T)
+        uint8 codes, winner (n, T) int32 with -1 = no entry, utility (n, T) float32)."""
+        b, n, dev = self.board, self.n, self.device
+        T = b["T"]
+        status = torch.zeros((n, T), dtype=torch.uint8, device=dev)
+        winner = torch.full((n, T), -1, dtype=torch.int32, device=dev)
+        util = torch.zeros((n, T), dtype=torch.float32, device=dev)
+        st, tt = b["status"], b["tab_task"]
+        rows = torch.arange(n, device=dev)[:, None]
+        m = st >= 0
+        status[rows.expand_as(st)[m], (st[m] >> 2).long()] = (st[m] & 3).to(torch.uint8)
+        m = tt >= 0
+        at = (rows.expand_as(tt)[m], tt[m].long())
+        winner[at] = b["tab_winner"][m]
+        util[at] = b["tab_util"][m]
+        return status, winner, util
+
+    def grow_board(self, status_slots=None, table_slots=None):
+        """More slots per agent (never fewer): the rows padded with empty slots, so that a refused
+        update_loop_board call can be repeated."""
+        b = self.board
+        ks = b["Ks"] if status_slots is None else int(status_slots)
+        kt = b["Kt"] if table_slots is None else int(table_slots)
+        for name, k, have in (("status_slots", ks, b["Ks"]), ("table_slots", kt, b["Kt"])):
+            if not have <= k <= _lib.BOARD_MAX_SLOTS:
+                raise ValueError(f"{name} must be in [{have}, {_lib.BOARD_MAX_SLOTS}], got {k}")
+
+        def pad(t, k, fill):
+            out = torch.full((t.shape[0], k), fill, dtype=t.dtype, device=t.device)
+            out[:, :t.shape[1]] = t
+            return out
+        for key, k, fill in (("status", ks, -1), ("claim_out", ks, -1), ("tab_task", kt, -1), ("tab_winner", kt, -1),
+                             ("tab_util", kt, 0), ("conflict_out", kt, -1)):
+            b[key] = pad(b[key], k, fill)
+        b["Ks"], b["Kt"] = ks, kt
+        return self
+
+    def write_back_board(self, agents, task_ids=None):
+        """write_back_tasks for the board of set_task_board: the non-OPEN statuses and the task_claims as the
+        loop left them; agents in input order, task_ids[k]: the dict key of board task k (default: the
+        tasks_from_dict keys given to set_task_board)."""
+        task_ids = self.board_task_ids if task_ids is None else task_ids
+        st = self.to_input_order(self.board_status())
+        tt, tw, tu = (self.to_input_order(t) for t in self.board_tables())
+        for i, a in enumerate(agents):
+            for e in st[i][st[i] >= 0]:
+                task = a.tasks.get(int(task_ids[int(e) >> 2]))
+                if task is not None:
+                    task["status"] = STATUS_NAMES[int(e) & 3]
+            a.task_claims = {int(task_ids[int(k)]): {"winner": int(w), "utility": float(u)}
+                             for k, w, u in zip(tt[i], tw[i], tu[i]) if k >= 0 and w >= 0}
+
     def _update_loop(self, ticks, sense_radius, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed,
-                     max_speed, mode, pull_frac, trace_every, radio_radius=None, tasks=None, channel=None) -> dict:
+                     max_speed, mode, pull_frac, trace_every, radio_radius=None, tasks=None, channel=None,
+                     board=None) -> dict:
         """update_loop (sense_radius None: the `sensors` lists, fixed), update_loop_sensed,
-        update_loop_radio (radio_radius given: no message graph) and update_loop_tasks (tasks: the board);
-        channel: (loss, loss_seed) with loss > 0 -- the two radio loops through swarm_update_loop_channel."""
+        update_loop_radio (radio_radius given: no message graph), update_loop_tasks (tasks: the board) and
+        update_loop_board (board: the sparse one); channel: (loss, loss_seed) with loss > 0 -- the two radio
+        loops through swarm_update_loop_channel."""
         ticks, trace_every = int(ticks), int(trace_every)
         if mode not in ("push", "pull", "hybrid"):
             raise ValueError(f"unknown mode {mode!r}")
@@ -1127,7 +1274,25 @@ class Swarm:
                                 *[tp(k) for k in ("status_lo", "status_hi", "claim_out", "conflict_out",
                                                   "tab_winner", "tab_util")])
                 task_counts = np.zeros((ticks, 3), np.int64)
-            if channel is not None:
+            if board is not None:
+                if board["status"].shape[0] != n:
+                    raise ValueError("the task board was set for another number of agents")
+                bs = _lib.BoardState(board["Ks"], board["Kt"], p(self.caps),
+                                     *[p(board[k]) for k in ("status", "tab_task", "tab_winner", "tab_util",
+                                                             "claim_out", "conflict_out")])
+                task_counts = np.zeros((ticks, 3), np.int64)
+                ch = _lib.Channel(channel[0], channel[1]) if channel is not None else None
+                link_counts = np.zeros((ticks, 2), np.int64)
+                over = _lib.BoardOverflow()
+                rc = _lib.lib().swarm_update_loop_board(
+                    *head, float(radio_radius), float(sense_radius), *tail, ctypes.byref(refused), board["handle"],
+                    ctypes.byref(bs), task_counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(guard),
+                    _lib.stream(), ctypes.byref(ch) if ch is not None else None,
+                    link_counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(over))
+                self.last_refused_tick = refused.value
+                self.last_board_overflow = None if over.kind == _lib.BOARD_FITS else \
+                    (BOARD_OVERFLOW_KINDS[over.kind], int(self.perm[over.agent]))
+            elif channel is not None:
                 ch = _lib.Channel(channel[0], channel[1])
                 link_counts = np.zeros((ticks, 2), np.int64)
                 rc = _lib.lib().swarm_update_loop_channel(
@@ -1162,7 +1327,7 @@ class Swarm:
         out = {"counts": counts, "singular": sing.value}
         if trace_every:
             out["trace"] = trace
-        if tasks is not None:
+        if tasks is not None or board is not None:
             out["task_counts"], out["guard"] = task_counts, guard.value
         if channel is not None:
             out["link_counts"] = link_counts

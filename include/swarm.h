@@ -896,6 +896,104 @@ int swarm_obstacle_field_set_velocities(swarm_ctx *ctx, swarm_obstacle_field *fi
 int swarm_obstacle_field_refresh(swarm_ctx *ctx, swarm_obstacle_field *field, swarm_obstacle_field_info *info,
                                  void *stream);
 
+/*
+ * The task loop on boards of any size (contract U1-B): swarm_update_loop_tasks / _channel word for
+ * word -- the receive, the two task handlers, the claim evaluation, the lossy channel, kills, the refusal of a
+ * too-dense tick -- with 0 <= T <= 2^24 tasks and every agent's task state stored sparsely.  The 64-task loop
+ * above is untouched and stays the faster one for the boards it takes.
+ *
+ * The board is a handle.  swarm_board_create copies tpos (device, T x 2 f64) and treq (device, T i8) and builds,
+ * on the host (one wait for the stream), a grid over the tasks' bounding box with cells at least 5 (1 + 1e-9)
+ * wide (at most 4 T + 1024 cells) and per cell its tasks in ascending index.  A task is claimed only within
+ * distance 4 and evaluated only when dx * dx + dy * dy <= 25, so an agent looks at the tasks of the 3 x 3 task
+ * cells around it and at no others; the grid only ever offers a superset, every offered task takes the loop's own
+ * pre-test.  SWARM_ERR_ARG, nothing created: a NULL ctx or out, T outside [0, 2^24] (refused before the device is
+ * touched), a NULL array with T > 0, a non-finite position, a box without a finite extent, a treq outside
+ * [-1, 31].  swarm_board_info fills *info; swarm_board_read (for tests and tools) copies the cells' offsets
+ * (ncx * ncy + 1 u32) and the cell-sorted task indices (T i32), either may be NULL.  swarm_board_destroy waits for
+ * the device, then frees the board; swarm_ctx_destroy frees the boards still alive.
+ *
+ * swarm_board_state: every agent's task state, on the device, in/out, sparse and canonical -- the final bytes do
+ * not depend on the order in which a kernel met the tasks, so a run cut into chunks equals the single run bit for
+ * bit.  Ks status slots and Kt table slots per agent, each in [1, 4096], chosen by the caller:
+ *   status        (n x Ks i32)  entries task << 2 | code, code 1 TENTATIVE, 2 LOCKED, 3 ASSIGNED (OPEN is never
+ *                 stored), strictly ascending by task, the empty slots -1 behind the last entry;
+ *   tab_task / tab_winner / tab_util  (n x Kt; i32, i32, f32)  the agent's task_claims ascending by task; an empty
+ *                 slot has task -1, winner -1, utility 0.  A table survives its owner losing leadership;
+ *   claim_out     (2 x n x Ks i32) / conflict_out (2 x n x Kt i32), by tick parity like the outbox: row
+ *                 ((t & 1) n + i) holds the tasks agent i claimed / sent at least one TASK_CONFLICT on during tick
+ *                 t, ascending, -1 behind the last.  The capacities suffice by construction: a claim takes a status
+ *                 slot on the tick it is sent, a conflict names an entry of its sender's table;
+ *   caps          (n u32) as swarm_allocate.
+ * The winner a conflict names is read from its sender's table as it stood at the end of the previous tick; a
+ * conflict on a task that table has no entry for (it can only come from a caller's arrays) reads as winner -1:
+ * everyone LOCKED.
+ *
+ * Overflow is a refusal.  An agent that needs a (Ks + 1)-th status or a (Kt + 1)-th table entry during tick t
+ * makes the call all or nothing, exactly as a too-dense tick does: SWARM_ERR_RANGE, *refused_tick = t, every
+ * caller array back to its entry bytes (these six included), the counts withheld; no thread writes past a row.
+ * *overflow (may be NULL) names the kind -- SWARM_BOARD_STATUS or SWARM_BOARD_TABLE, SWARM_BOARD_FITS otherwise
+ * -- and one agent (storage index) that overflowed; when several do in that tick, any of them.  Both counts only
+ * grow, so the refused tick is the first one at whose end the exact run holds more than the capacity.
+ *
+ * Entry checks, SWARM_ERR_ARG with nothing written: one device pass before any kernel indexes with a caller's
+ * value -- every entry -1 or a task in [0, T), every status code in 1..3, every row strictly ascending with the
+ * empties last (its verdict comes back with the entry bounding box's wait); a capacity outside [1, 4096]; a NULL
+ * ctx, board, state or array; a board of another ctx; and whatever swarm_update_loop_channel refuses.
+ * T == 0: swarm_update_loop_radio / its lossy form, task_counts zeroed, *n_guard = 0, no state array touched.
+ * Arguments: swarm_update_loop_channel's with (board, state) in place of tasks, then overflow.  ch == NULL or
+ * ch->loss == 0: the ideal channel, link_counts not written.
+ */
+typedef struct swarm_board swarm_board;
+
+typedef struct {
+    int64_t T;       /* tasks */
+    int64_t ncx;     /* the grid: ncx x ncy cells of side `cell` from (xmin, ymin) */
+    int64_t ncy;
+    double cell;
+    double xmin;
+    double ymin;
+    int64_t longest; /* the longest cell list */
+} swarm_board_desc;
+
+typedef struct {
+    int32_t Ks;
+    int32_t Kt;
+    const uint32_t *caps;
+    int32_t *status;
+    int32_t *tab_task;
+    int32_t *tab_winner;
+    float *tab_util;
+    int32_t *claim_out;
+    int32_t *conflict_out;
+} swarm_board_state;
+
+#define SWARM_BOARD_FITS 0
+#define SWARM_BOARD_STATUS 1
+#define SWARM_BOARD_TABLE 2
+
+typedef struct {
+    int32_t kind;    /* SWARM_BOARD_* */
+    int32_t pad;
+    int64_t agent;   /* storage index, -1 when nothing overflowed */
+} swarm_board_overflow;
+
+int swarm_board_create(swarm_ctx *ctx, int64_t T, const double *tpos, const int8_t *treq, swarm_board **out,
+                       swarm_board_desc *info, void *stream);
+int swarm_board_info(const swarm_board *board, swarm_board_desc *info);
+int swarm_board_read(const swarm_board *board, uint32_t *cell_off_host, int32_t *idx_host);
+int swarm_board_destroy(swarm_ctx *ctx, swarm_board *board);
+
+int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                            const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                            double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
+                            int32_t n_kill, double *vel, double *target, uint8_t *has_target, int64_t m,
+                            const double *obstacles, double radio_radius, double sense_radius, double max_speed,
+                            double *trace, int32_t trace_every, int64_t *counts, int64_t *n_singular,
+                            int64_t *refused_tick, const swarm_board *board, const swarm_board_state *state,
+                            int64_t *task_counts, int64_t *n_guard, void *stream, const swarm_channel *ch,
+                            int64_t *link_counts, swarm_board_overflow *overflow);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,7 +64,11 @@ def guard_flag(u, thr=20.0):
     return False
 
 
-def ref_loop_tasks(mod, inp, task_seed):
+def ref_loop_tasks(mod, inp, task_seed, n_tasks=N_TASKS, stat_from=0):
+    """n_tasks: the board's size (tools/gen_golden_loop_board.py hands out more than the 64 the words below can
+    hold: they then carry the tasks below 64 only, and stat["claim_sets"] / stat["conflict_sets"] the last two
+    ticks' sets as index lists).  stat_from: the observers' figures count tasks with this index and above."""
+    N_TASKS = n_tasks
     n = len(inp["ids"])
     ids = inp["ids"]
     wide = int(ids.max()) > 255
@@ -84,6 +88,7 @@ def ref_loop_tasks(mod, inp, task_seed):
     out_cur = [[] for _ in range(n)]
     stat = dict(handled=0, replaced=0, reaffirmed=0, overwritten=0, sent=0, min_gap=math.inf, guard=0)
     claim_heard = {}  # (sender id, task, its tick) -> leaders that handled it
+    task_of = {}  # id(an agent's task dict) -> its index
     L, W = mod.AgentState.LEADER, mod.AgentState.ELECTION_WAIT
     tcounts = np.zeros((ticks, 3), np.int64)
     now_t = [0]
@@ -107,13 +112,13 @@ def ref_loop_tasks(mod, inp, task_seed):
             k, u = struct.unpack("!If", payload)
             if a.state == L:
                 tcounts[now_t[0] - 1, 1] += 1
-                stat["handled"] += 1
+                stat["handled"] += k >= stat_from
                 claim_heard[(sender, k, now_t[0] - 1)] += 1
                 held = a.task_claims.get(k)
                 if held and u > held["utility"] + 5.0:
-                    stat["replaced"] += 1
+                    stat["replaced"] += k >= stat_from
                 elif held and held["winner"] != sender:
-                    stat["reaffirmed"] += 1
+                    stat["reaffirmed"] += k >= stat_from
             real(sender, payload)
         a._handle_task_claim = claim
 
@@ -122,13 +127,14 @@ def ref_loop_tasks(mod, inp, task_seed):
             before = a.tasks[k]["status"]
             real(sender, payload)
             if before in ("LOCKED", "ASSIGNED") and a.tasks[k]["status"] != before:
-                stat["overwritten"] += 1
+                stat["overwritten"] += k >= stat_from
         a._handle_task_conflict = conflict
 
         def util(task, a=a, real=a._calculate_utility):
             u = real(task)
-            stat["min_gap"] = min(stat["min_gap"], abs(u - 20.0))
-            stat["guard"] += guard_flag(u)
+            if task_of.get(id(task), 0) >= stat_from:
+                stat["min_gap"] = min(stat["min_gap"], abs(u - 20.0))
+                stat["guard"] += guard_flag(u)
             return u
         a._calculate_utility = util
     obstacles = [tuple(float(v) for v in o) for o in inp["obs"]]
@@ -157,6 +163,7 @@ def ref_loop_tasks(mod, inp, task_seed):
                 a.tasks = {}
                 for k in range(N_TASKS):
                     a.tasks[k] = {"status": "OPEN", "pos": (float(tx[k]), float(ty[k]))}
+                    task_of[id(a.tasks[k])] = k
                     if req[k] >= 0:
                         a.tasks[k]["required_cap"] = CAP_NAMES[req[k]]
         hears = heard([(a.position[0], a.position[1]) for a in agents])
@@ -205,13 +212,21 @@ def ref_loop_tasks(mod, inp, task_seed):
     hdr = 9 if wide else 6
     claim_out = np.zeros((2, n), np.uint64)
     conflict_out = np.zeros((2, n), np.uint64)
+    stat["claim_sets"] = [[set() for _ in range(n)] for _ in range(2)]
+    stat["conflict_sets"] = [[set() for _ in range(n)] for _ in range(2)]
     for tk, sent in ((ticks - 1, last_two[0]), (ticks, last_two[1])):
         for i in range(n):
             for pk in sent[i]:
                 if pk[0] == 4:
-                    claim_out[tk & 1, i] |= np.uint64(1) << np.uint64(struct.unpack("!If", pk[hdr:])[0])
+                    k = struct.unpack("!If", pk[hdr:])[0]
+                    stat["claim_sets"][tk & 1][i].add(k)
+                    if k < 64:
+                        claim_out[tk & 1, i] |= np.uint64(1) << np.uint64(k)
                 if pk[0] == 5:
-                    conflict_out[tk & 1, i] |= np.uint64(1) << np.uint64(struct.unpack(conf_fmt, pk[hdr:])[0])
+                    k = struct.unpack(conf_fmt, pk[hdr:])[0]
+                    stat["conflict_sets"][tk & 1][i].add(k)
+                    if k < 64:
+                        conflict_out[tk & 1, i] |= np.uint64(1) << np.uint64(k)
     mod.struct, mod.time, mod.random = struct, time, __import__("random")
     status = np.array([[gg.STATUS_CODE[a.tasks[k]["status"]] for k in range(N_TASKS)] for a in agents], np.uint8)
     tabw = np.full((n, N_TASKS), -1, np.int32)
@@ -222,7 +237,7 @@ def ref_loop_tasks(mod, inp, task_seed):
             tabu[i, k] = c["utility"]  # an unpacked '!f': exactly an f32
             assert float(tabu[i, k]) == c["utility"]
     stat["sent"] = int(tcounts[:, 0].sum())
-    stat["unheard"] = sum(1 for v in claim_heard.values() if v == 0)
+    stat["unheard"] = sum(1 for (_, k, _), v in claim_heard.items() if v == 0 and k >= stat_from)
     assert len(claim_heard) == stat["sent"]
     out = dict(
         state_out=np.array([a.state.value for a in agents], np.uint8),
