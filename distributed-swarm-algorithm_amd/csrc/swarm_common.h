@@ -67,6 +67,11 @@ enum Slot {
     S_TASK_COUNTS,    // task update loop: the per-tick task counters (sharded) and their sums
     S_TASK_SENDERS,   // task update loop: one byte per agent and tick parity, what it sent (outbox + task bits)
     S_LINK_COUNTS,    // lossy update loops: the per-tick link counters (sharded) and their sums
+    S_REORDER_BITS,   // reorder: the entry checks' verdict word and the permutation check's bitmap (1 bit per row)
+    S_REORDER_INV,    // reorder: the inverse of a permutation (n int32)
+    S_REORDER_DEG,    // reorder: the relabelled rows' degrees (n + 1 int32); the plan's moved-row counter
+    S_REORDER_POS,    // reorder: the positions in input order (n x 2 f64)
+    S_REORDER_ORDER,  // reorder: the cell order of the input positions (n int32)
     S_NUM
 };
 

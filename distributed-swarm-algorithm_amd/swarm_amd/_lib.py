@@ -43,7 +43,8 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_obstacle_field_destroy", "swarm_update_loop_channel", "swarm_link_dropped",
            "swarm_obstacle_field_create_moving", "swarm_obstacle_field_set_velocities",
            "swarm_obstacle_field_refresh", "swarm_board_create", "swarm_board_info", "swarm_board_read",
-           "swarm_board_destroy", "swarm_update_loop_board")
+           "swarm_board_destroy", "swarm_update_loop_board", "swarm_permute_rows", "swarm_graph_relabel",
+           "swarm_resort_plan")
 BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
 BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
 
@@ -82,6 +83,11 @@ class BoardState(ctypes.Structure):
     _fields_ = [("Ks", ctypes.c_int32), ("Kt", ctypes.c_int32)] + \
                [(k, ctypes.c_void_p) for k in ("caps", "status", "tab_task", "tab_winner", "tab_util", "claim_out",
                                                "conflict_out")]
+
+
+class Rows(ctypes.Structure):
+    """swarm_rows: one array of swarm_permute_rows (device pointers)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_bytes", ctypes.c_int64)]
 
 
 class BoardOverflow(ctypes.Structure):
@@ -246,6 +252,9 @@ def load(path: str = LIB_PATH):
         L.swarm_update_loop_board.argtypes = L.swarm_update_loop_radio.argtypes[:-1] + [
             P, ctypes.POINTER(BoardState), P, ctypes.POINTER(i64), P, ctypes.POINTER(Channel), P,
             ctypes.POINTER(BoardOverflow)]
+        L.swarm_permute_rows.argtypes = [P, i64, P, i32, ctypes.POINTER(Rows), P]
+        L.swarm_graph_relabel.argtypes = [P, i64, P, P, P, P, P, P]
+        L.swarm_resort_plan.argtypes = [P, i64, P, P, d, P, P, ctypes.POINTER(i64), P]
         for name in EXPORTS:
             if name not in ("swarm_last_error", "swarm_version"):
                 getattr(L, name).restype = ctypes.c_int

@@ -327,6 +327,8 @@ class Swarm:
         self.leader = torch.empty(n, dtype=torch.int32, device=dev)
         self.state = torch.full((n,), _lib.FOLLOWER, dtype=torch.uint8, device=dev)
         self._id_index = None
+        self.resorts = 0            # resort() calls that changed the storage order
+        self.last_resort_moved = 0  # rows the last resort() moved
 
     # ------------------------------------------------------------------ graph
     @property
@@ -1332,6 +1334,133 @@ class Swarm:
         if channel is not None:
             out["link_counts"] = link_counts
         return out
+
+    # ------------------------------------------------------------------ storage order (R1)
+    def _resort_arrays(self):
+        """Every per-agent array the swarm holds, as (put, tensor, halves): put(new) stores its replacement;
+        halves = 2 for the arrays kept by tick parity (2 n rows: both halves take the same permutation)."""
+        out = []
+
+        def attr(name, halves=1):
+            out.append((lambda t, name=name: setattr(self, name, t), getattr(self, name), halves))
+
+        def item(d, key, halves=1):
+            out.append((lambda t, d=d, key=key: d.__setitem__(key, t), d[key], halves))
+        for name in ("ids", "pos", "caps", "leader", "state"):
+            attr(name)
+        if hasattr(self, "vel"):
+            for name in ("vel", "target", "has_target"):
+                attr(name)
+        if hasattr(self, "pos_prev") and self._pos_prev_valid():
+            attr("pos_prev")
+        if hasattr(self, "tick_off"):
+            attr("tick_off")
+        if hasattr(self, "fsm"):
+            for key in ("last_hb", "wait_start", "delay", "leader_pos", "has_leader_pos", "alive"):
+                item(self.fsm, key)
+            item(self.fsm, "outbox", 2)
+        if hasattr(self, "tasks"):
+            for key in ("status_lo", "status_hi", "tab_winner", "tab_util"):
+                item(self.tasks, key)
+            for key in ("claim_out", "conflict_out"):
+                item(self.tasks, key, 2)
+        if hasattr(self, "board"):
+            for key in ("status", "tab_task", "tab_winner", "tab_util"):
+                item(self.board, key)
+            for key in ("claim_out", "conflict_out"):
+                item(self.board, key, 2)
+        return out
+
+    def _pos_prev_valid(self) -> bool:
+        """self.pos_prev is one tick behind self.pos (the next loop call would keep it)."""
+        k = getattr(self, "_pos_prev_key", None)
+        return k is not None and k[0] is self.pos and k[1] == self.pos._version
+
+    def _relabelled(self, frm, row_ptr, col):
+        """(row_ptr, col) in the numbering of `frm` (swarm_graph_relabel), as new tensors."""
+        rp = torch.empty_like(row_ptr)
+        cl = torch.empty_like(col)
+        _lib.check(_lib.lib().swarm_graph_relabel(
+            _lib.ctx(), self.n, _lib.ptr(frm, torch.int32), _lib.ptr(row_ptr, torch.int32),
+            _lib.ptr(col, torch.int32) if col.numel() else None, _lib.ptr(rp), _lib.ptr(cl) if cl.numel() else None,
+            _lib.stream()))
+        return rp, cl
+
+    def resort(self):
+        """Restore the spatial storage order after the agents have moved (contract R1): the swarm
+        becomes, array for array and byte for byte, the Swarm one would construct from the input-order view of
+        its state.  self.perm is swarm_cell_order of the current positions in input order (agents of a cell by
+        input index); every per-agent array -- ids, pos, caps, leader, state, the motion state, a valid pos_prev,
+        tick_off, the fsm, the 64-task board's and the task board's arrays, the parity halves of the outboxes
+        included -- moves by one row permutation on the device (swarm_permute_rows), so to_input_order of each
+        is bit for bit what it was; the neighbour graph names the same neighbours in the same row order in the
+        new indices (swarm_graph_relabel; the hearers of a directed graph are its transpose with ascending
+        rows, as set_graph builds them).  The election then finds its 16-bit columns again and allocate() its
+        cell index.  Tensors are replaced, never overwritten, and only after every device call has gone
+        through: a failure leaves the swarm as it was (SwarmError ERR_ARG for a NaN or infinite position).
+        Results of earlier calls (ElectResult.leader, AllocResult.won, traces, ...) stay in the storage order
+        of their time: self.resorts counts the calls that changed the order, so a holder can tell.
+        self.last_resort_moved: the rows whose index changed; 0 (no agent changes index, or n <= 1) rewrites
+        nothing and keeps every tensor's identity.  layout="input" raises ValueError: the caller asked for its
+        own numbering."""
+        if self.layout == "input":
+            raise ValueError("resort: the swarm was made with layout='input', which keeps the caller's numbering")
+        n, dev = self.n, self.device
+        if n <= 1:
+            self.last_resort_moved = 0
+            return self
+        L = _lib.lib()
+        frm = torch.empty(n, dtype=torch.int32, device=dev)
+        perm = torch.empty(n, dtype=torch.int32, device=dev)
+        moved = ctypes.c_int64(0)
+        with torch.cuda.device(dev):
+            _lib.check(L.swarm_resort_plan(_lib.ctx(), n, _lib.ptr(self.pos, torch.float64),
+                                           _lib.ptr(self.perm, torch.int32), self.cell, _lib.ptr(frm), _lib.ptr(perm),
+                                           ctypes.byref(moved), _lib.stream()))
+            if moved.value == 0:
+                self.last_resort_moved = 0
+                return self
+            arrays = [a for a in self._resort_arrays() if a[1].numel()]
+            new, descs = [], []
+            for _put, t, halves in arrays:
+                if not t.is_contiguous() or t.shape[0] != halves * n:
+                    raise ValueError("resort: a per-agent array is not contiguous or was set for another n")
+                out = torch.empty_like(t)
+                rb = t.element_size() * (t.numel() // (halves * n))
+                new.append(out)
+                descs += [_lib.Rows(t.data_ptr() + h * n * rb, out.data_ptr() + h * n * rb, rb) for h in range(halves)]
+            for lo in range(0, len(descs), 64):
+                part = descs[lo:lo + 64]
+                _lib.check(L.swarm_permute_rows(_lib.ctx(), n, _lib.ptr(frm), len(part),
+                                                (_lib.Rows * len(part))(*part), _lib.stream()))
+            graph = hear = None
+            if self.row_ptr is not None:
+                graph = self._relabelled(frm, self.row_ptr, self.col)
+                if getattr(self, "_hear", None) is not None:
+                    # the transpose's rows are ascending in set_graph: sorted again in the new indices
+                    hrp, hcol = self._relabelled(frm, *self._hear)
+                    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev),
+                                                   (hrp[1:] - hrp[:-1]).long())
+                    hear = (hrp, (torch.sort(rows * n + hcol.long())[0] % n).to(torch.int32))
+        pos_prev_kept = hasattr(self, "pos_prev") and self._pos_prev_valid()
+        for (put, _t, _h), out in zip(arrays, new):
+            put(out)
+        self.perm = perm
+        if graph is not None:
+            self.row_ptr, self.col = graph
+            self._hear = hear
+        # everything keyed on the old order
+        self._c16 = self._rp64 = self._again = self._id_index = None
+        self._cindex = self._cindex_key = self._cindex_bad = None
+        if pos_prev_kept:
+            self._pos_prev_key = (self.pos, self.pos._version)
+        else:
+            self._pos_prev_key = None
+            if hasattr(self, "pos_prev"):
+                del self.pos_prev
+        self.resorts += 1
+        self.last_resort_moved = moved.value
+        return self
 
     # ------------------------------------------------------------------ views / bridge
     def to_input_order(self, storage_tensor) -> np.ndarray:

@@ -994,6 +994,54 @@ int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             int64_t *task_counts, int64_t *n_guard, void *stream, const swarm_channel *ch,
                             int64_t *link_counts, swarm_board_overflow *overflow);
 
+/*
+ * Restoring the spatial storage order of a moved swarm (contract R1).  No reference counterpart: the
+ * reference keeps its agents in a Python list.  Three calls: the order (swarm_resort_plan), the per-agent arrays
+ * moved into it (swarm_permute_rows), the neighbour graph renamed to it (swarm_graph_relabel).  Every value that
+ * indexes memory is checked on the device before it is used, and SWARM_ERR_ARG means that nothing was written.
+ *
+ * swarm_permute_rows: dst row k = src row from[k], for each of `count` arrays of n rows of row_bytes bytes
+ * (device), in one pass: the rows of 1, 2, 4, 8 or 16 bytes whose src and dst are aligned to their width share one
+ * launch, any other row is copied by ceil(row_bytes / 16) lanes (16, 4 or 1 bytes per lane, by what base and width
+ * allow).  `from` (device, n) must be a permutation of [0, n): one bitmap pass (a 64-bit atomic OR per row), its
+ * verdict read with one host wait, before any dst byte is written.  SWARM_ERR_ARG: a NULL ctx / from / arrays /
+ * src / dst, n outside [0, 2^31), count outside [0, 64], a row_bytes outside [1, 16384] (a task board row of 4096
+ * slots), a dst that overlaps a src, another dst or `from` (host pointer ranges; a src may be given twice), a
+ * `from` that names a row outside [0, n) or a row twice.  All of these but the last are refused before the device
+ * is touched.  n == 0 and count == 0 are no-ops.
+ */
+typedef struct swarm_rows {
+    const void *src;
+    void *dst;
+    int64_t row_bytes;
+} swarm_rows;
+
+int swarm_permute_rows(swarm_ctx *ctx, int64_t n, const int32_t *from, int32_t count, const swarm_rows *arrays,
+                       void *stream);
+
+/*
+ * The CSR (row_ptr, col) in a new numbering: out row k = in row from[k], every column c replaced by to[c] (to =
+ * the inverse of from), the order inside a row kept.  row_ptr_out (device, n + 1) and col_out (device, row_ptr[n])
+ * are the caller's.  Checked before anything is written, with one host wait: `from` as swarm_permute_rows checks
+ * it, row_ptr starting at 0 and never decreasing, every column in [0, n) (the columns index `to`); row_ptr[n] is
+ * taken as the length of col.  SWARM_ERR_ARG for any of these, for a NULL pointer (col and col_out may be NULL for
+ * a graph without edges), n outside [0, 2^31 - 1) and an output that overlaps an input or the other output.
+ */
+int swarm_graph_relabel(swarm_ctx *ctx, int64_t n, const int32_t *from, const int32_t *row_ptr, const int32_t *col,
+                        int32_t *row_ptr_out, int32_t *col_out, void *stream);
+
+/*
+ * The canonical order of contract R1 for agents stored as pos (device, n x 2 f64, storage order) with perm[k] the
+ * input index of storage row k: perm_out (device, n) is what swarm_cell_order gives for the positions in input
+ * order with `cell` -- agents of one cell in ascending INPUT index, whatever their storage order was -- and
+ * from[k] (device, n) is the current storage row of the agent that belongs in row k; *moved (host) counts the rows
+ * with from[k] != k.  Waits for the stream.  SWARM_ERR_ARG, nothing written: what swarm_cell_order refuses (a
+ * position that is NaN or infinite, a box without a finite extent), a perm that is not a permutation of [0, n)
+ * (the bitmap pass above), a NULL pointer, an output that overlaps an input or the other output.
+ */
+int swarm_resort_plan(swarm_ctx *ctx, int64_t n, const double *pos, const int32_t *perm, double cell, int32_t *from,
+                      int32_t *perm_out, int64_t *moved, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
