@@ -151,6 +151,7 @@ int swarm_ctx_destroy(swarm_ctx *ctx) {
         (void)hipDeviceSynchronize();  // a field or a board may still be read by queued work
     for (swarm_obstacle_field *f : ctx->fields) swarm::free_obstacle_field(f);
     for (swarm_board *b : ctx->boards) swarm::free_board(b);
+    for (swarm_board *b : ctx->board_graves) swarm::free_board(b);
     for (int s = 0; s < swarm::S_NUM; ++s)
         if (ctx->slot[s]) (void)hipFree(ctx->slot[s]);
     if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);

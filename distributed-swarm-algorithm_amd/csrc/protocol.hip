@@ -1720,6 +1720,7 @@ struct TickRun {
     const swarm_board *board = nullptr;  // U1-B (T > 0: swarm_update_loop_board), with its state and overflow info
     const swarm_board_state *bstate = nullptr;
     swarm_board_overflow *overflow = nullptr;
+    swarm_board *mboard = nullptr;  // U1-M: `board` again when it moves (its lists advance after every tick)
     bool tasked() const { return tasks && tasks->T > 0; }
     bool boarded() const { return board && board->T > 0; }
     bool lossy() const { return ch && ch->loss > 0.0; }
@@ -2035,14 +2036,16 @@ struct BoardState {
         const swarm_board_state &q = *r.bstate;
         const size_t un = size_t(r.n), in = size_t((k.t - 1) & 1) * un, out = size_t(k.t & 1) * un;
         const size_t ks = size_t(q.Ks), kt = size_t(q.Kt);
+        // (U1-M) a moving board: the tick's lists on the call's grid, the claim handler's positions one advance behind
+        const Grid &tg = b.moving ? b.call_g : b.g;
         const BoardTick bt{q.Ks,
                            q.Kt,
                            int32_t(k.t - r.t0 - 1),
-                           reinterpret_cast<const double2 *>(b.tpos),
+                           reinterpret_cast<const double2 *>(b.moving ? b.lag : b.tpos),
                            b.treq,
-                           BoardGrid{b.cell_off, reinterpret_cast<const double2 *>(b.sxy),
-                                     reinterpret_cast<const int2 *>(b.sir), b.g.xmin, b.g.ymin, b.g.xmax, b.g.ymax,
-                                     b.g.inv_cell, b.g.ncx, b.g.ncy},
+                           BoardGrid{b.moving ? b.dyn_off : b.cell_off, reinterpret_cast<const double2 *>(b.sxy),
+                                     reinterpret_cast<const int2 *>(b.sir), tg.xmin, tg.ymin, tg.xmax, tg.ymax,
+                                     tg.inv_cell, tg.ncx, tg.ncy},
                            q.caps,
                            q.status,
                            q.tab_task,
@@ -2228,6 +2231,8 @@ int read_back(const TickRun &r, const Counters &c, const LoopSense *ls, const En
         if (const int rc = snap.restore_if_refused(ls->st, s)) return rc;
     if (ls && mov)  // (contract O2) the list is the field's own array: back to its entry bits as well
         if (const int rc = moving_field_restore_if_refused(mov, ls->st, s)) return rc;
+    if (ls && r.boarded() && r.mboard)  // (contract U1-M) the board's two lists likewise
+        if (const int rc = moving_board_restore_if_refused(r.mboard, ls->st, s)) return rc;
     if (!(r.traffic || ls || want_sing || r.counts || want_tasks || want_links)) return SWARM_OK;
     // the sums that are asked for, one after the other from [16]: counts, task counts, link counts
     const size_t words = size_t(r.ticks) * 4, cnt_bytes = r.counts ? words * 8 : 0;
@@ -2304,10 +2309,13 @@ int run_ticks(const TickRun &r) {
     if (sensed) {
         if (mov && (rc = moving_field_fetch(mov, s))) return rc;
         if (boarded && (rc = BoardState::check_entry(r, s))) return rc;
+        // (contract U1-M) the box of the tasks' spans over the call comes to the host with that wait as well
+        if (boarded && r.mboard && (rc = moving_board_box(r.mboard, r.dt, r.ticks, s))) return rc;
         if ((rc = loop_sense_begin(r.ctx, r.n, loop->pos, loop->sense_radius, r.ticks, r.dt, loop->max_speed, &ls, s,
                                    radio ? loop->radio_radius : 0.0)))
             return rc;
         if (boarded && (rc = BoardState::entry_verdict(r))) return rc;
+        if (boarded && r.mboard && (rc = moving_board_begin(r.mboard, s))) return rc;
         if (mov && (rc = moving_field_begin(mov, r.ticks, r.dt, true, s))) return rc;
         if ((rc = snap.take(r, s))) return rc;
     }
@@ -2344,6 +2352,8 @@ int run_ticks(const TickRun &r) {
         // far beyond the agents: offsets by search)
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
         if (radio) rs.bind(ls);
+        // (contract U1-M) the cell lists of Q_{t-1} before the tick's launches, the advance after them
+        if (boarded && r.mboard && (rc = moving_board_tick(r.mboard, s))) return rc;
         auto window_tick = [&](auto ch) {
             return boarded  ? bs.launch(r, f, k, rs, ls.st, ch, s)
                    : tasked ? ts.launch(r, f, k, rs, ch, s)
@@ -2354,6 +2364,7 @@ int run_ticks(const TickRun &r) {
              : push  ? ps.launch(r, f, k, vec, cnt.tr_shards, s)
                      : launch_tick_pull(r, grid, f, k, s);
         if (rc) return rc;
+        if (boarded && r.mboard && (rc = moving_board_advance(r.mboard, ls.st, r.dt, s))) return rc;
         if (loop && (rc = tick_physics(r, f, ls, t, &cur, &lag, cnt.sing, s))) return rc;
     }
     if (loop && cur != loop->pos) {  // an odd number of ticks: pos <- P_end, pos_prev <- P_{end-1}
@@ -2553,6 +2564,35 @@ int swarm_update_loop_channel(swarm_ctx *ctx, int64_t n, const int32_t *ids, dou
                                  tasks, task_counts, n_guard, ch, link_counts});
 }
 
+// swarm_update_loop_board (mboard NULL) and swarm_update_loop_board_moving (mboard == board).
+static int board_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                      const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
+                      double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks, int32_t n_kill,
+                      double *vel, double *target, uint8_t *has_target, int64_t m, const double *obstacles,
+                      double radio_radius, double sense_radius, double max_speed, double *trace,
+                      int32_t trace_every, int64_t *counts, int64_t *n_singular, int64_t *refused_tick,
+                      const swarm_board *board, swarm_board *mboard, const swarm_board_state *state,
+                      int64_t *task_counts, int64_t *n_guard, void *stream, const swarm_channel *ch,
+                      int64_t *link_counts, swarm_board_overflow *overflow) {
+    using namespace swarm;
+    if (overflow) *overflow = swarm_board_overflow{SWARM_BOARD_FITS, 0, -1};
+    if (const int rc = check_channel(ch)) return rc;
+    if (const int rc = check_board(ctx, n, board, state)) return rc;
+    SW_ARG(board->moving == (mboard != nullptr),
+           mboard ? "the board does not move (swarm_update_loop_board takes it)"
+                  : "a moving board needs swarm_update_loop_board_moving (this loop would read it as a frozen board)");
+    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
+                        trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
+    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
+              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream,
+              nullptr, task_counts, n_guard, ch, link_counts};
+    r.board = board;
+    r.mboard = mboard;
+    r.bstate = state;
+    r.overflow = overflow;
+    return run_loop(kLoopRadio, r);
+}
+
 int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
                             const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks, double dt,
                             double timeout, double jitter, uint64_t seed, const int64_t *kill_ticks,
@@ -2562,19 +2602,26 @@ int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             int64_t *refused_tick, const swarm_board *board, const swarm_board_state *state,
                             int64_t *task_counts, int64_t *n_guard, void *stream, const swarm_channel *ch,
                             int64_t *link_counts, swarm_board_overflow *overflow) {
-    using namespace swarm;
-    if (overflow) *overflow = swarm_board_overflow{SWARM_BOARD_FITS, 0, -1};
-    if (const int rc = check_channel(ch)) return rc;
-    if (const int rc = check_board(ctx, n, board, state)) return rc;
-    const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
-                        trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
-    TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
-              timeout, jitter, seed, kill_ticks, n_kill, -1.0, counts, nullptr, &loop, stream,
-              nullptr, task_counts, n_guard, ch, link_counts};
-    r.board = board;
-    r.bstate = state;
-    r.overflow = overflow;
-    return run_loop(kLoopRadio, r);
+    return board_loop(ctx, n, ids, pos, pos_prev, tick_off, fsm, t0, ticks, dt, timeout, jitter, seed, kill_ticks,
+                      n_kill, vel, target, has_target, m, obstacles, radio_radius, sense_radius, max_speed, trace,
+                      trace_every, counts, n_singular, refused_tick, board, nullptr, state, task_counts, n_guard,
+                      stream, ch, link_counts, overflow);
+}
+
+int swarm_update_loop_board_moving(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                                   const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
+                                   double dt, double timeout, double jitter, uint64_t seed,
+                                   const int64_t *kill_ticks, int32_t n_kill, double *vel, double *target,
+                                   uint8_t *has_target, int64_t m, const double *obstacles, double radio_radius,
+                                   double sense_radius, double max_speed, double *trace, int32_t trace_every,
+                                   int64_t *counts, int64_t *n_singular, int64_t *refused_tick, swarm_board *board,
+                                   const swarm_board_state *state, int64_t *task_counts, int64_t *n_guard,
+                                   void *stream, const swarm_channel *ch, int64_t *link_counts,
+                                   swarm_board_overflow *overflow) {
+    return board_loop(ctx, n, ids, pos, pos_prev, tick_off, fsm, t0, ticks, dt, timeout, jitter, seed, kill_ticks,
+                      n_kill, vel, target, has_target, m, obstacles, radio_radius, sense_radius, max_speed, trace,
+                      trace_every, counts, n_singular, refused_tick, board, board, state, task_counts, n_guard, stream,
+                      ch, link_counts, overflow);
 }
 
 int swarm_link_dropped(uint64_t seed, int64_t t, int32_t sid, int32_t rid, double loss) {

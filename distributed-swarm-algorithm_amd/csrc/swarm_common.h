@@ -140,11 +140,28 @@ struct swarm_board {
     int64_t longest = 0;
     std::vector<uint32_t> cell_off_host;
     std::vector<int32_t> idx_host;
+    // A moving board (contract U1-M; task_board.hip): `tpos` is the current list `cur`, in/out; `sxy`
+    // and `sir` are rewritten by every tick's device build; the members above describe the creation list (or the
+    // last refresh).  The key and value buffers are T long; dyn_off and cub_tmp grow on demand.
+    bool moving = false;
+    double *lag = nullptr;            // device: T x 2, the list one advance behind `cur` (the claim handler's)
+    double *vel = nullptr;            // device: T x 2
+    double *entry = nullptr;          // device: cur then lag as they were at a loop's entry (a refused tick)
+    double *box = nullptr;            // device: the span-box reduction's partials, then its four doubles
+    uint32_t *keys[2] = {};           // device: the tasks' cell keys, by task and sorted
+    int32_t *vals[2] = {};            // device: the task indices, by task and sorted
+    uint32_t *dyn_off = nullptr;      // device: the tick's cell offsets
+    void *cub_tmp = nullptr;          // device: hipCUB's temporary storage
+    size_t cap_cells = 0, cap_tmp = 0;  // what the two buffers above hold
+    swarm::Grid call_g{};             // the call's grid
 };
 
 struct swarm_ctx {
     std::vector<swarm_obstacle_field *> fields;  // the live obstacle fields created on this ctx
     std::vector<swarm_board *> boards;           // the live task boards created on this ctx
+    // The boards destroyed last (their memory freed, the structs kept): a new board cannot take the address of a
+    // handle that has just died, so a stale handle is told from a live board whatever the allocator does.
+    std::vector<swarm_board *> board_graves;
     swarm::AucPersist auc;         // sharded auction between begin and the round calls
     int device = 0;
     void *slot[swarm::S_NUM] = {};
@@ -221,6 +238,16 @@ inline bool live_board(const swarm_ctx *ctx, const swarm_board *b) {
         if (q == b) return true;
     return false;
 }
+// A moving board's call (contract U1-M; task_board.hip), in the order a loop uses them: the span-box reduction
+// queued before the call's entry wait (its four doubles land in verdict_host[1..4]); after the wait the call's
+// grid, the buffers and the entry snapshot (SWARM_ERR_ARG before anything is written: a box without a finite
+// extent); per tick the cell lists of `cur` on that grid, then -- after the tick's kernels -- lag <- cur and the
+// advance, nothing once the stop word is set; at the end both lists back to their entry bytes if it is.
+int moving_board_box(swarm_board *b, double dt, int32_t ticks, hipStream_t s);
+int moving_board_begin(swarm_board *b, hipStream_t s);
+int moving_board_tick(swarm_board *b, hipStream_t s);
+int moving_board_advance(swarm_board *b, const unsigned long long *st, double dt, hipStream_t s);
+int moving_board_restore_if_refused(swarm_board *b, const unsigned long long *st, hipStream_t s);
 
 }  // namespace swarm
 

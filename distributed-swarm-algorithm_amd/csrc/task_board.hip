@@ -1,22 +1,55 @@
 // Task boards (contract U1-B): the host side.  The grid and the cell lists are built by task_grid.h
 // from a host copy of the caller's board -- once per board, one host wait, not the hot path -- and uploaded as
-// a cell-sorted copy of (x, y, treq, index); protocol.hip's board kernels read them.
+// a cell-sorted copy of (x, y, treq, index); protocol.hip's board kernels read them.  A moving board (contract
+// U1-M) rebuilds that copy on the device before every tick, with no host wait (below).
 #include <cmath>
 #include <cstring>
 #include <new>
 
+#include "binning.h"
 #include "swarm_common.h"
 #include "task_grid.h"
+#include "task_motion.h"
 #include "utility.h"
 
 namespace swarm {
 
-void free_board(swarm_board *b) {
-    if (!b) return;
-    void *const dev[] = {b->tpos, b->treq, b->cell_off, b->sxy, b->sir, b->verdict};
+namespace {
+
+// Frees everything a board owns; the struct itself stays, an empty board.
+void release_board(swarm_board *b) {
+    void *const dev[] = {b->tpos,    b->treq,    b->cell_off, b->sxy,     b->sir,     b->verdict, b->lag,    b->vel,
+                         b->entry,   b->box,     b->keys[0],  b->keys[1], b->vals[0], b->vals[1], b->dyn_off, b->cub_tmp};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (b->verdict_host) (void)hipHostFree(b->verdict_host);
+    *b = swarm_board();
+}
+
+constexpr size_t kBoardGraves = 16;
+
+// A destroyed board: what it owned is freed, the struct is kept on the ctx's list of the last few that died (the
+// oldest of them deleted), so that its address is not handed to the next board.
+void bury_board(swarm_ctx *ctx, swarm_board *b) {
+    release_board(b);
+    auto &g = ctx->board_graves;
+    try {
+        g.push_back(b);
+    } catch (const std::bad_alloc &) {
+        delete b;
+        return;
+    }
+    if (g.size() > kBoardGraves) {
+        delete g.front();
+        g.erase(g.begin());
+    }
+}
+
+}  // namespace
+
+void free_board(swarm_board *b) {
+    if (!b) return;
+    release_board(b);
     delete b;
 }
 
@@ -62,13 +95,251 @@ swarm_board_desc describe(const swarm_board &b) {
     return swarm_board_desc{b.T, b.g.ncx, b.g.ncy, b.g.cell, b.g.xmin, b.g.ymin, b.longest};
 }
 
+// ---- moving boards (contract U1-M): the cell-sorted copy built on the device, every tick ----
+//
+// The builder is build_task_cells on the device: the tasks' cell keys on the call's grid (binning.h's k_cell_keys:
+// cell_coord's arithmetic, which task_cell_coord restates), a stable radix sort of (key, task index) -- a cell's
+// tasks keep ascending task index, the host builder's list -- the offsets by search, and one gather that writes
+// the 16-byte (x, y) rows and the 8-byte (index, treq) rows in sorted order.  No atomics: the same lists on every
+// run.  Every index that addresses memory comes from the sort's values, 0 .. T - 1 by construction (the gather
+// checks it all the same).
+
+constexpr unsigned kBoxParts = 1024;  // workgroups of the span-box reduction, at most
+
+// The box of every task's span over the call (task_motion.h, the same functions): per workgroup four doubles.
+__global__ __launch_bounds__(kBlock) void k_task_span_box(int64_t T, const double2 *__restrict__ cur,
+                                                         const double2 *__restrict__ vel, double dt, int32_t ticks,
+                                                         double *__restrict__ part) {
+    TaskBox b{kBoxEmptyLo, kBoxEmptyLo, kBoxEmptyHi, kBoxEmptyHi};
+    for (int64_t k = int64_t(blockIdx.x) * kBlock + threadIdx.x; k < T; k += int64_t(gridDim.x) * kBlock) {
+        const double2 p = cur[k], v = vel[k];
+        task_box_add(&b, p.x, p.y, v.x, v.y, dt, ticks);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        b.xmin = fmin(b.xmin, __shfl_xor(b.xmin, off, 64));
+        b.ymin = fmin(b.ymin, __shfl_xor(b.ymin, off, 64));
+        b.xmax = fmax(b.xmax, __shfl_xor(b.xmax, off, 64));
+        b.ymax = fmax(b.ymax, __shfl_xor(b.ymax, off, 64));
+    }
+    __shared__ double s[4][kBlock / kWave];
+    const int wid = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s[0][wid] = b.xmin; s[1][wid] = b.ymin; s[2][wid] = b.xmax; s[3][wid] = b.ymax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / kWave; ++w) {
+            s[0][0] = fmin(s[0][0], s[0][w]); s[1][0] = fmin(s[1][0], s[1][w]);
+            s[2][0] = fmax(s[2][0], s[2][w]); s[3][0] = fmax(s[3][0], s[3][w]);
+        }
+        part[4 * blockIdx.x + 0] = s[0][0]; part[4 * blockIdx.x + 1] = s[1][0];
+        part[4 * blockIdx.x + 2] = s[2][0]; part[4 * blockIdx.x + 3] = s[3][0];
+    }
+}
+
+// The cell-sorted copy: row q is task svals[q].  Loads gather, stores are coalesced 16- and 8-byte rows.
+__global__ __launch_bounds__(kBlock) void k_task_gather(int64_t T, const int32_t *__restrict__ svals,
+                                                       const double2 *__restrict__ cur,
+                                                       const int8_t *__restrict__ treq, double2 *__restrict__ sxy,
+                                                       int2 *__restrict__ sir) {
+    for (int64_t q = int64_t(blockIdx.x) * kBlock + threadIdx.x; q < T; q += int64_t(gridDim.x) * kBlock) {
+        const int32_t k = svals[q];
+        if (k < 0 || k >= T) continue;
+        sxy[q] = cur[k];
+        sir[q] = make_int2(k, int(treq[k]));
+    }
+}
+
+// The contract's advance, one pass: lag <- cur, cur <- fl(cur + fl(v * dt)) per coordinate (-ffp-contract=off:
+// two roundings).  Nothing once the run's stop word is set.
+__global__ __launch_bounds__(kBlock) void k_task_advance(const unsigned long long *__restrict__ st, int64_t T,
+                                                        double2 *__restrict__ cur, double2 *__restrict__ lag,
+                                                        const double2 *__restrict__ vel, double dt) {
+    if (st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    for (int64_t k = int64_t(blockIdx.x) * kBlock + threadIdx.x; k < T; k += int64_t(gridDim.x) * kBlock) {
+        const double2 p = cur[k], v = vel[k];
+        lag[k] = p;
+        cur[k] = make_double2(task_advance(p.x, v.x, dt), task_advance(p.y, v.y, dt));
+    }
+}
+
+// Both lists back to their entry bytes when a tick of the loop was refused (obstacle_field.hip's k_obs_restore).
+__global__ __launch_bounds__(kBlock) void k_task_restore(const unsigned long long *__restrict__ st, int64_t T,
+                                                        double2 *__restrict__ cur, double2 *__restrict__ lag,
+                                                        const double2 *__restrict__ entry) {
+    if (st[0] == 0) return;
+    for (int64_t k = int64_t(blockIdx.x) * kBlock + threadIdx.x; k < T; k += int64_t(gridDim.x) * kBlock) {
+        cur[k] = entry[k];
+        lag[k] = entry[T + k];
+    }
+}
+
+int sort_end_bit(int64_t ncells) {
+    int b = 1;
+    while (b < 32 && (int64_t(1) << b) < ncells) ++b;
+    return b;
+}
+
+// p <- a device buffer of at least `bytes`, *have its size: grown by a new allocation (hipFree waits for the
+// device: no queued work reads the old one).
+int grow(void **p, size_t *have, size_t bytes) {
+    if (*p && *have >= bytes) return SWARM_OK;
+    bytes = bytes < 64 ? 64 : bytes;
+    if (*p) SW_HIP(hipFree(*p));
+    *p = nullptr, *have = 0;
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        set_error("out of device memory for %zu bytes of a moving task board", bytes);
+        return SWARM_ERR_OOM;
+    }
+    *have = bytes;
+    return SWARM_OK;
+}
+
+// The board's buffers for a grid of `ncells` cells.
+int size_buffers(swarm_board *b, int64_t ncells, hipStream_t s) {
+    size_t off_bytes = b->cap_cells * 4;
+    void *off = b->dyn_off;
+    int rc = grow(&off, &off_bytes, (size_t(ncells) + 1) * 4);
+    b->dyn_off = static_cast<uint32_t *>(off), b->cap_cells = off_bytes / 4;
+    if (rc) return rc;
+    size_t sort_bytes = 0;
+    if (b->T)
+        SW_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, b->keys[0], b->keys[1], b->vals[0], b->vals[1],
+                                                  int(b->T), 0, sort_end_bit(ncells), s));
+    return grow(&b->cub_tmp, &b->cap_tmp, sort_bytes);
+}
+
+// The cell-sorted copy of `cur` on grid g, queued on s (size_buffers has run for g's cell count).
+int build_lists(swarm_board *b, const Grid &g, hipStream_t s) {
+    const int64_t T = b->T, ncells = g.ncx * g.ncy;
+    if (T) {
+        hipLaunchKernelGGL(k_cell_keys, dim3(grid_for(T, kBlock, 8192)), dim3(kBlock), 0, s,
+                           reinterpret_cast<const double2 *>(b->tpos), T, g, b->keys[0], b->vals[0]);
+        SW_LAUNCHED();
+        size_t tmp = b->cap_tmp;
+        SW_HIP(hipcub::DeviceRadixSort::SortPairs(b->cub_tmp, tmp, b->keys[0], b->keys[1], b->vals[0], b->vals[1],
+                                                  int(T), 0, sort_end_bit(ncells), s));
+    }
+    hipLaunchKernelGGL(k_cell_offsets_search, dim3(grid_for(ncells + 1, kBlock, 8192)), dim3(kBlock), 0, s, b->keys[1],
+                       T, ncells, b->dyn_off);
+    SW_LAUNCHED();
+    if (T) {
+        hipLaunchKernelGGL(k_task_gather, dim3(grid_for(T, kBlock, 8192)), dim3(kBlock), 0, s, T, b->vals[1],
+                           reinterpret_cast<const double2 *>(b->tpos), b->treq, reinterpret_cast<double2 *>(b->sxy),
+                           reinterpret_cast<int2 *>(b->sir));
+        SW_LAUNCHED();
+    }
+    return SWARM_OK;
+}
+
+int motion_error(TaskMotionStatus st) {
+    switch (st) {
+    case kTaskMotionOk:
+        return SWARM_OK;
+    case kTaskMotionNonFinite:
+        set_error("invalid argument: a task position or velocity is not finite");
+        return SWARM_ERR_ARG;
+    default:
+        set_error("invalid argument: the moving tasks' positions have no finite extent over the call");
+        return SWARM_ERR_ARG;
+    }
+}
+
+// The device velocities (NULL: zero) to the host, refused unless finite.
+int fetch_velocities(int64_t T, const double *velocities, std::vector<double> *out, hipStream_t s) {
+    try {
+        out->assign(size_t(T) * 2, 0.0);
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory for %lld velocities", static_cast<long long>(T));
+        return SWARM_ERR_OOM;
+    }
+    if (T && velocities) {
+        SW_HIP(hipMemcpyAsync(out->data(), velocities, size_t(T) * 16, hipMemcpyDeviceToHost, s));
+        SW_HIP(hipStreamSynchronize(s));
+    }
+    SW_ARG(task_velocities_finite(T, out->data()), "a velocity is not finite");
+    return SWARM_OK;
+}
+
+// What a moving board owns beyond a static one (on any error the caller frees b).
+int make_moving(swarm_board *b, const std::vector<double> &h_vel, hipStream_t s) {
+    const size_t T = size_t(b->T), rows = T ? T : 1;
+    SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->lag), rows * 16));
+    SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->vel), rows * 16));
+    SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->entry), rows * 32));
+    SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->box), (size_t(kBoxParts) + 1) * 32));
+    for (int q = 0; q < 2; ++q) {
+        SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->keys[q]), rows * 4));
+        SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->vals[q]), rows * 4));
+    }
+    if (T) {
+        SW_HIP(hipMemcpyAsync(b->lag, b->tpos, T * 16, hipMemcpyDeviceToDevice, s));  // at creation lag = cur
+        SW_HIP(hipMemcpyAsync(b->vel, h_vel.data(), T * 16, hipMemcpyHostToDevice, s));
+    }
+    SW_HIP(hipStreamSynchronize(s));
+    b->moving = true;
+    b->call_g = b->g;
+    return size_buffers(b, b->g.ncx * b->g.ncy, s);
+}
+
+// The span-box reduction of the list as it stands, its four doubles at b->box + 4 kBoxParts.
+int launch_span_box(swarm_board *b, double dt, int32_t ticks, hipStream_t s) {
+    const unsigned np = grid_for(b->T, kBlock, kBoxParts);
+    hipLaunchKernelGGL(k_task_span_box, dim3(np), dim3(kBlock), 0, s, b->T, reinterpret_cast<const double2 *>(b->tpos),
+                       reinterpret_cast<const double2 *>(b->vel), dt, ticks, b->box);
+    SW_LAUNCHED();
+    hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(64), 0, s, b->box, int(np), b->box + 4 * size_t(kBoxParts));
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
 }  // namespace
+
+int moving_board_box(swarm_board *b, double dt, int32_t ticks, hipStream_t s) {
+    if (const int rc = launch_span_box(b, dt, ticks, s)) return rc;
+    double *h = reinterpret_cast<double *>(b->verdict_host + 1);
+    h[2] = HUGE_VAL;  // (overwritten by the copy: a wait that never came reads as a refusal)
+    SW_HIP(hipMemcpyAsync(h, b->box + 4 * size_t(kBoxParts), 32, hipMemcpyDeviceToHost, s));
+    return SWARM_OK;
+}
+
+int moving_board_begin(swarm_board *b, hipStream_t s) {
+    const double *h = reinterpret_cast<const double *>(b->verdict_host + 1);
+    Grid g{};
+    int rc;
+    if ((rc = motion_error(task_grid_of_box(b->T, TaskBox{h[0], h[1], h[2], h[3]}, &g)))) return rc;
+    if ((rc = size_buffers(b, g.ncx * g.ncy, s))) return rc;
+    b->call_g = g;
+    const size_t T = size_t(b->T);
+    SW_HIP(hipMemcpyAsync(b->entry, b->tpos, T * 16, hipMemcpyDeviceToDevice, s));
+    SW_HIP(hipMemcpyAsync(b->entry + 2 * T, b->lag, T * 16, hipMemcpyDeviceToDevice, s));
+    return SWARM_OK;
+}
+
+int moving_board_tick(swarm_board *b, hipStream_t s) { return build_lists(b, b->call_g, s); }
+
+int moving_board_advance(swarm_board *b, const unsigned long long *st, double dt, hipStream_t s) {
+    hipLaunchKernelGGL(k_task_advance, dim3(grid_for(b->T, kBlock, 4096)), dim3(kBlock), 0, s, st, b->T,
+                       reinterpret_cast<double2 *>(b->tpos), reinterpret_cast<double2 *>(b->lag),
+                       reinterpret_cast<const double2 *>(b->vel), dt);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
+int moving_board_restore_if_refused(swarm_board *b, const unsigned long long *st, hipStream_t s) {
+    hipLaunchKernelGGL(k_task_restore, dim3(grid_for(b->T, kBlock, 4096)), dim3(kBlock), 0, s, st, b->T,
+                       reinterpret_cast<double2 *>(b->tpos), reinterpret_cast<double2 *>(b->lag),
+                       reinterpret_cast<const double2 *>(b->entry));
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
+
 }  // namespace swarm
 
-extern "C" {
-
-int swarm_board_create(swarm_ctx *ctx, int64_t T, const double *tpos, const int8_t *treq, swarm_board **out,
-                       swarm_board_desc *info, void *stream) {
+// swarm_board_create (moving false) and swarm_board_create_moving.
+static int create_board(swarm_ctx *ctx, int64_t T, const double *tpos, const int8_t *treq, bool moving,
+                        const double *velocities, swarm_board **out, swarm_board_desc *info, void *stream) {
     using namespace swarm;
     SW_ARG(ctx != nullptr && out != nullptr, "ctx or out is NULL");
     SW_ARG(T >= 0 && T <= kMaxBoardTasks, "T must be in [0, 2^24]");
@@ -103,6 +374,9 @@ int swarm_board_create(swarm_ctx *ctx, int64_t T, const double *tpos, const int8
         set_error("out of host memory for the board's cell lists");
         return SWARM_ERR_OOM;
     }
+    std::vector<double> h_vel;
+    if (moving)  // its own refusal, before anything is created
+        if (const int rc = fetch_velocities(T, velocities, &h_vel, s)) return rc;
     swarm_board *b = new (std::nothrow) swarm_board();
     if (!b) {
         set_error("out of host memory");
@@ -111,7 +385,9 @@ int swarm_board_create(swarm_ctx *ctx, int64_t T, const double *tpos, const int8
     b->T = T;
     b->g = tc.g;
     b->longest = tc.longest;
-    if (const int rc = upload_board(b, h_pos, h_req, tc, s)) {
+    int rc = upload_board(b, h_pos, h_req, tc, s);
+    if (!rc && moving) rc = make_moving(b, h_vel, s);
+    if (rc) {
         free_board(b);
         return rc;
     }
@@ -126,6 +402,102 @@ int swarm_board_create(swarm_ctx *ctx, int64_t T, const double *tpos, const int8
     }
     if (info) *info = describe(*b);
     *out = b;
+    return SWARM_OK;
+}
+
+extern "C" {
+
+int swarm_board_create(swarm_ctx *ctx, int64_t T, const double *tpos, const int8_t *treq, swarm_board **out,
+                       swarm_board_desc *info, void *stream) {
+    return create_board(ctx, T, tpos, treq, false, nullptr, out, info, stream);
+}
+
+int swarm_board_create_moving(swarm_ctx *ctx, int64_t T, const double *tpos, const int8_t *treq,
+                              const double *velocities, swarm_board **out, swarm_board_desc *info, void *stream) {
+    return create_board(ctx, T, tpos, treq, true, velocities, out, info, stream);
+}
+
+int swarm_board_set_velocities(swarm_ctx *ctx, swarm_board *board, const double *velocities, void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr && board != nullptr, "ctx or board is NULL");
+    SW_ARG(live_board(ctx, board), "the board is not a live board of this ctx");
+    SW_ARG(board->moving, "the board does not move (swarm_board_create_moving makes one that does)");
+    if (!ctx_on_current_device(ctx)) return SWARM_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<double> h_vel;
+    if (const int rc = fetch_velocities(board->T, velocities, &h_vel, s)) return rc;
+    if (board->T) {
+        SW_HIP(hipMemcpyAsync(board->vel, h_vel.data(), size_t(board->T) * 16, hipMemcpyHostToDevice, s));
+        SW_HIP(hipStreamSynchronize(s));
+    }
+    return SWARM_OK;
+}
+
+int swarm_board_positions(const swarm_board *board, const double **cur, const double **lag) {
+    using namespace swarm;
+    SW_ARG(board != nullptr && cur != nullptr && lag != nullptr, "board, cur or lag is NULL");
+    *cur = board->tpos;
+    *lag = board->moving ? board->lag : board->tpos;
+    return SWARM_OK;
+}
+
+int swarm_board_call_box(swarm_ctx *ctx, swarm_board *board, double dt, int32_t ticks, double *box_host,
+                         void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr && board != nullptr && box_host != nullptr, "ctx, board or box_host is NULL");
+    SW_ARG(live_board(ctx, board), "the board is not a live board of this ctx");
+    SW_ARG(board->moving, "the board does not move (swarm_board_create_moving makes one that does)");
+    SW_ARG(ticks >= 0 && std::isfinite(dt), "ticks or dt out of range");
+    if (!ctx_on_current_device(ctx)) return SWARM_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = moving_board_box(board, dt, ticks, s)) return rc;
+    SW_HIP(hipStreamSynchronize(s));
+    memcpy(box_host, board->verdict_host + 1, 32);
+    return SWARM_OK;
+}
+
+int swarm_board_refresh(swarm_ctx *ctx, swarm_board *board, swarm_board_desc *info, void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr && board != nullptr, "ctx or board is NULL");
+    SW_ARG(live_board(ctx, board), "the board is not a live board of this ctx");
+    if (!ctx_on_current_device(ctx)) return SWARM_ERR_ARG;
+    swarm_board *b = board;
+    if (b->moving) {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const size_t T = size_t(b->T);
+        std::vector<double> h_pos;
+        std::vector<uint32_t> off;
+        std::vector<int32_t> idx;
+        Grid g{};
+        int rc;
+        try {
+            h_pos.resize(T * 2);
+            idx.resize(T);
+            if (T) {
+                SW_HIP(hipMemcpyAsync(h_pos.data(), b->tpos, T * 16, hipMemcpyDeviceToHost, s));
+                SW_HIP(hipStreamSynchronize(s));
+            }
+            if ((rc = motion_error(task_static_grid(b->T, h_pos.data(), &g)))) return rc;
+            const int64_t ncells = g.ncx * g.ncy;
+            off.resize(size_t(ncells) + 1);
+            if ((rc = size_buffers(b, ncells, s))) return rc;
+            if ((rc = build_lists(b, g, s))) return rc;
+            SW_HIP(hipMemcpyAsync(off.data(), b->dyn_off, off.size() * 4, hipMemcpyDeviceToHost, s));
+            if (T) SW_HIP(hipMemcpyAsync(idx.data(), b->vals[1], T * 4, hipMemcpyDeviceToHost, s));
+            SW_HIP(hipStreamSynchronize(s));
+        } catch (const std::bad_alloc &) {
+            set_error("out of host memory for the board's cell lists");
+            return SWARM_ERR_OOM;
+        }
+        int64_t longest = 0;
+        for (size_t c = 0; c + 1 < off.size(); ++c)
+            longest = int64_t(off[c + 1] - off[c]) > longest ? int64_t(off[c + 1] - off[c]) : longest;
+        b->g = g;
+        b->longest = longest;
+        b->cell_off_host = std::move(off);
+        b->idx_host = std::move(idx);
+    }
+    if (info) *info = describe(*b);
     return SWARM_OK;
 }
 
@@ -155,7 +527,7 @@ int swarm_board_destroy(swarm_ctx *ctx, swarm_board *board) {
     if (!ctx_on_current_device(ctx)) return SWARM_ERR_ARG;
     SW_HIP(hipDeviceSynchronize());  // queued work may still read the board
     v.erase(it);
-    free_board(board);
+    bury_board(ctx, board);
     return SWARM_OK;
 }
 

@@ -44,7 +44,8 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_obstacle_field_create_moving", "swarm_obstacle_field_set_velocities",
            "swarm_obstacle_field_refresh", "swarm_board_create", "swarm_board_info", "swarm_board_read",
            "swarm_board_destroy", "swarm_update_loop_board", "swarm_permute_rows", "swarm_graph_relabel",
-           "swarm_resort_plan")
+           "swarm_resort_plan", "swarm_board_create_moving", "swarm_board_set_velocities", "swarm_board_positions",
+           "swarm_board_refresh", "swarm_board_call_box", "swarm_update_loop_board_moving")
 BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
 BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
 
@@ -252,6 +253,12 @@ def load(path: str = LIB_PATH):
         L.swarm_update_loop_board.argtypes = L.swarm_update_loop_radio.argtypes[:-1] + [
             P, ctypes.POINTER(BoardState), P, ctypes.POINTER(i64), P, ctypes.POINTER(Channel), P,
             ctypes.POINTER(BoardOverflow)]
+        L.swarm_board_create_moving.argtypes = [P, i64, P, P, P, ctypes.POINTER(P), ctypes.POINTER(BoardDesc), P]
+        L.swarm_board_set_velocities.argtypes = [P, P, P, P]
+        L.swarm_board_positions.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P)]
+        L.swarm_board_refresh.argtypes = [P, P, ctypes.POINTER(BoardDesc), P]
+        L.swarm_board_call_box.argtypes = [P, P, d, i32, P, P]
+        L.swarm_update_loop_board_moving.argtypes = L.swarm_update_loop_board.argtypes
         L.swarm_permute_rows.argtypes = [P, i64, P, i32, ctypes.POINTER(Rows), P]
         L.swarm_graph_relabel.argtypes = [P, i64, P, P, P, P, P, P]
         L.swarm_resort_plan.argtypes = [P, i64, P, P, d, P, P, ctypes.POINTER(i64), P]

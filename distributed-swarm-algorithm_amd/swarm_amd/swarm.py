@@ -127,6 +127,16 @@ def _destroy_field(ctx, handle):
     handle.value = None
 
 
+def _board_velocities(v, T):
+    """set_task_board / set_board_velocities: a (T, 2) float64 array of finite velocities."""
+    vel = np.ascontiguousarray(np.asarray(v, np.float64))
+    if vel.shape != (T, 2):
+        raise ValueError(f"velocities: expected shape ({T}, 2), got {tuple(vel.shape)}")
+    if not np.isfinite(vel).all():
+        raise ValueError("velocities must be finite")
+    return vel
+
+
 def _destroy_board(ctx, handle):
     """A task board's finalizer (set_task_board), as _destroy_field."""
     L = _lib._lib
@@ -1080,13 +1090,17 @@ class Swarm:
                              for k, tid in enumerate(task_ids) if w[i, k] >= 0}
 
     # ------------------------------------------------------------------ task loop on boards of any size (U1-B)
-    def set_task_board(self, tx, ty=None, treq=None, *, status_slots: int = 16, table_slots: int = 16):
+    def set_task_board(self, tx, ty=None, treq=None, *, status_slots: int = 16, table_slots: int = 16,
+                       velocities=None):
         """set_tasks for a board of up to 2^24 tasks (contract U1-B; swarm_board_create): every task OPEN at
         every agent, every claim table empty, nothing in flight, the per-agent state sparse -- status_slots
         non-OPEN statuses and table_slots claim-table entries per agent at most, each in [1, 4096].  An agent
         that needs one more makes update_loop_board refuse the call (grow_board, then repeat it).  Arguments as
         set_tasks, a tasks_from_dict result included; the positions and treq are checked here, by the library
-        (SwarmError ERR_ARG).  The 64-task board of set_tasks is a separate one and is left alone."""
+        (SwarmError ERR_ARG).  The 64-task board of set_tasks is a separate one and is left alone.
+        velocities ((T, 2), finite): a moving board (contract U1-M; swarm_board_create_moving) -- after every tick
+        of update_loop_board each task advances by fl(v * dt), the cell grid is rebuilt on the device before every
+        tick, and a claim is heard with the positions it was sent with; board_positions() reads them back."""
         import weakref
         ids = None
         if ty is None and isinstance(tx, tuple) and len(tx) == 4:
@@ -1105,6 +1119,7 @@ class Swarm:
         for name, k in (("status_slots", ks), ("table_slots", kt)):
             if not 1 <= k <= _lib.BOARD_MAX_SLOTS:
                 raise ValueError(f"{name} must be in [1, {_lib.BOARD_MAX_SLOTS}], got {k}")
+        vel = None if velocities is None else _board_velocities(velocities, T)
         old = getattr(self, "board", None)
         if old is not None:
             old["finalizer"]()
@@ -1113,11 +1128,18 @@ class Swarm:
             tpos = torch.as_tensor(np.stack([tx, ty], 1), device=dev).contiguous()
             rq = torch.as_tensor(tq.astype(np.int8), device=dev)
             ctx = _lib.ctx()
-            _lib.check(_lib.lib().swarm_board_create(ctx, T, _lib.ptr(tpos) if T else None,
-                                                     _lib.ptr(rq) if T else None, ctypes.byref(handle),
-                                                     ctypes.byref(desc), _lib.stream()))
+            if vel is None:
+                _lib.check(_lib.lib().swarm_board_create(ctx, T, _lib.ptr(tpos) if T else None,
+                                                         _lib.ptr(rq) if T else None, ctypes.byref(handle),
+                                                         ctypes.byref(desc), _lib.stream()))
+            else:
+                dv = torch.as_tensor(vel, device=dev)
+                _lib.check(_lib.lib().swarm_board_create_moving(ctx, T, _lib.ptr(tpos) if T else None,
+                                                                _lib.ptr(rq) if T else None,
+                                                                _lib.ptr(dv) if T else None, ctypes.byref(handle),
+                                                                ctypes.byref(desc), _lib.stream()))
         e = lambda rows, k: torch.full((rows, k), -1, dtype=torch.int32, device=dev)  # noqa: E731
-        self.board = dict(T=T, handle=handle, ctx=ctx, Ks=ks, Kt=kt,
+        self.board = dict(T=T, handle=handle, ctx=ctx, Ks=ks, Kt=kt, moving=vel is not None,
                           info={k: getattr(desc, k) for k, _ in _lib.BoardDesc._fields_},
                           status=e(n, ks), tab_task=e(n, kt), tab_winner=e(n, kt),
                           tab_util=torch.zeros((n, kt), dtype=torch.float32, device=dev),
@@ -1147,6 +1169,35 @@ class Swarm:
         return self._update_loop(ticks, sense_radius, obstacles, None, kill_ticks, dt, timeout, jitter, seed,
                                  max_speed, "pull", 0.125, trace_every, radio_radius=radio_radius, board=self.board,
                                  channel=channel)
+
+    def board_positions(self):
+        """The board's two position lists by task index, (cur, lag), each a (T, 2) float64 numpy array: a static
+        board's positions twice; a moving board's (contract U1-M) current positions and those one advance behind
+        (equal until the first tick)."""
+        b = self.board
+        T = b["T"]
+        cur, lag = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(_lib.lib().swarm_board_positions(b["handle"], ctypes.byref(cur), ctypes.byref(lag)))
+        out = np.zeros((T, 2)), np.zeros((T, 2))
+        if T:
+            with torch.cuda.device(self.device):
+                torch.cuda.current_stream().synchronize()
+                for a, p in zip(out, (cur, lag)):
+                    _lib.copy_to_host(a, p)
+        return out
+
+    def set_board_velocities(self, v):
+        """New velocities ((T, 2), finite) for the moving board of set_task_board(velocities=...); neither position
+        list changes (swarm_board_set_velocities)."""
+        b = self.board
+        if not b.get("moving"):
+            raise RuntimeError("the task board does not move: call set_task_board(..., velocities=...)")
+        vel = _board_velocities(v, b["T"])
+        with torch.cuda.device(self.device):
+            dv = torch.as_tensor(vel, device=self.device)
+            _lib.check(_lib.lib().swarm_board_set_velocities(b["ctx"], b["handle"], _lib.ptr(dv) if b["T"] else None,
+                                                             _lib.stream()))
+        return self
 
     def board_status(self) -> torch.Tensor:
         """(n, status_slots) int32 sparse status rows, storage order: task << 2 | code (1 TENTATIVE, 2 LOCKED,
@@ -1286,7 +1337,9 @@ class Swarm:
                 ch = _lib.Channel(channel[0], channel[1]) if channel is not None else None
                 link_counts = np.zeros((ticks, 2), np.int64)
                 over = _lib.BoardOverflow()
-                rc = _lib.lib().swarm_update_loop_board(
+                entry = _lib.lib().swarm_update_loop_board_moving if board.get("moving") else \
+                    _lib.lib().swarm_update_loop_board
+                rc = entry(
                     *head, float(radio_radius), float(sense_radius), *tail, ctypes.byref(refused), board["handle"],
                     ctypes.byref(bs), task_counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(guard),
                     _lib.stream(), ctypes.byref(ch) if ch is not None else None,

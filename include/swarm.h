@@ -995,6 +995,61 @@ int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, doubl
                             int64_t *link_counts, swarm_board_overflow *overflow);
 
 /*
+ * Moving tasks (contract U1-M): the board's cell grid rebuilt on the device every tick.
+ * A moving board is a board (U1-B) with one velocity (vx, vy) per task.  It owns two position lists by task
+ * index, `cur` and `lag` (T x 2 f64 each), and the velocities (T x 2 f64).  With Q_0 the creation positions:
+ *   Reading.    Tick t of a call runs U1-B (U1-L when lossy) word for word with cur = Q_{t-1}: the grid, the far
+ *               pre-test, the utility, the guard flag and the claim evaluation.  The claims of tick t-1 are heard
+ *               with lag = Q_{t-2}: the handler recomputes the utility a claim was sent with.
+ *   Advancing.  After the tick's kernels lag[k] = cur[k], then cur[k] = fl(cur[k] + fl(v[k] * dt)) per
+ *               coordinate, the product and the sum rounded separately.
+ *   In/out.     At creation lag = cur.  Both lists persist across calls: a run cut into chunks is the single run
+ *               bit for bit.  swarm_board_set_velocities changes neither list.
+ *   Refusals.   A refused tick (a status or table overflow, a too-dense tick: SWARM_ERR_RANGE, all or nothing)
+ *               leaves both lists at their entry bytes, like the sparse rows.  A call with n == 0, T == 0 or
+ *               ticks == 0 runs no tick and advances nothing.
+ * Per tick the cell-sorted copy is built on the call's stream with no host wait: the tasks' cell keys on the
+ * call's grid, a stable radix sort of (key, task index), the offsets by search, one gather of the (x, y) and
+ * (index, treq) rows -- no atomics, every cell's tasks in ascending index, the host builder's lists.  The call's
+ * grid covers the box of every task's span over `ticks` advances (csrc/task_motion.h has the proof that every
+ * position of the call lies inside; an agent more than 6 beyond the box skips its task window), reduced on the
+ * device and read with the call's existing entry wait.  SWARM_ERR_ARG, nothing written: a span that overflows or
+ * a box without a finite extent.
+ *
+ * swarm_board_create_moving: swarm_board_create plus velocities (device, T x 2 f64; NULL: all zero).
+ * SWARM_ERR_ARG, nothing created: a non-finite velocity, and whatever swarm_board_create refuses.
+ * swarm_board_set_velocities (waits for the stream; NULL: all zero): SWARM_ERR_ARG on a static board or a
+ * non-finite entry, nothing changed.
+ * swarm_board_positions: the device pointers of cur and lag (a static board: its positions, twice); reading them
+ * after a call is how the positions come back.
+ * swarm_board_refresh (for tests and tools; waits): rebuilds the cell lists with the device builder for the
+ * current list, on the grid swarm_board_create would choose for it, and fills *info; swarm_board_read then returns
+ * those lists.  On a static board it only fills *info.
+ * swarm_board_call_box (for tests and tools; waits): the device's span-box reduction for a call of `ticks` ticks
+ * of dt, box_host = (xmin, ymin, xmax, ymax); xmax = +inf when a span is not finite.
+ * swarm_update_loop_board_moving: swarm_update_loop_board's arguments with a moving board (SWARM_ERR_ARG for a
+ * static one).  swarm_update_loop_board is unchanged for static boards and refuses a moving board with
+ * SWARM_ERR_ARG, nothing written.
+ */
+int swarm_board_create_moving(swarm_ctx *ctx, int64_t T, const double *tpos, const int8_t *treq,
+                              const double *velocities, swarm_board **out, swarm_board_desc *info, void *stream);
+int swarm_board_set_velocities(swarm_ctx *ctx, swarm_board *board, const double *velocities, void *stream);
+int swarm_board_positions(const swarm_board *board, const double **cur, const double **lag);
+int swarm_board_refresh(swarm_ctx *ctx, swarm_board *board, swarm_board_desc *info, void *stream);
+int swarm_board_call_box(swarm_ctx *ctx, swarm_board *board, double dt, int32_t ticks, double *box_host,
+                         void *stream);
+int swarm_update_loop_board_moving(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,
+                                   const int32_t *tick_off, const swarm_fsm *fsm, int64_t t0, int32_t ticks,
+                                   double dt, double timeout, double jitter, uint64_t seed,
+                                   const int64_t *kill_ticks, int32_t n_kill, double *vel, double *target,
+                                   uint8_t *has_target, int64_t m, const double *obstacles, double radio_radius,
+                                   double sense_radius, double max_speed, double *trace, int32_t trace_every,
+                                   int64_t *counts, int64_t *n_singular, int64_t *refused_tick, swarm_board *board,
+                                   const swarm_board_state *state, int64_t *task_counts, int64_t *n_guard,
+                                   void *stream, const swarm_channel *ch, int64_t *link_counts,
+                                   swarm_board_overflow *overflow);
+
+/*
  * Restoring the spatial storage order of a moved swarm (contract R1).  No reference counterpart: the
  * reference keeps its agents in a Python list.  Three calls: the order (swarm_resort_plan), the per-agent arrays
  * moved into it (swarm_permute_rows), the neighbour graph renamed to it (swarm_graph_relabel).  Every value that

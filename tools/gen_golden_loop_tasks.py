@@ -64,10 +64,12 @@ def guard_flag(u, thr=20.0):
     return False
 
 
-def ref_loop_tasks(mod, inp, task_seed, n_tasks=N_TASKS, stat_from=0):
+def ref_loop_tasks(mod, inp, task_seed, n_tasks=N_TASKS, stat_from=0, before_tick=None):
     """n_tasks: the board's size (tools/gen_golden_loop_board.py hands out more than the 64 the words below can
     hold: they then carry the tasks below 64 only, and stat["claim_sets"] / stat["conflict_sets"] the last two
-    ticks' sets as index lists).  stat_from: the observers' figures count tasks with this index and above."""
+    ticks' sets as index lists).  stat_from: the observers' figures count tasks with this index and above.
+    before_tick(t, agents, board, trng): called at the start of every tick from the hand-out on, after the board is
+    handed out (tools/gen_golden_moving_tasks.py moves the tasks with it)."""
     N_TASKS = n_tasks
     n = len(inp["ids"])
     ids = inp["ids"]
@@ -166,6 +168,8 @@ def ref_loop_tasks(mod, inp, task_seed, n_tasks=N_TASKS, stat_from=0):
                     task_of[id(a.tasks[k])] = k
                     if req[k] >= 0:
                         a.tasks[k]["required_cap"] = CAP_NAMES[req[k]]
+        if before_tick is not None and board is not None:
+            before_tick(t, agents, board, trng)
         hears = heard([(a.position[0], a.position[1]) for a in agents])
         for i, a in enumerate(agents):
             if not alive[i]:
