@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -105,6 +106,20 @@ def _fast_ptr(t):
     """Device pointer of a tensor this module made or owns (contiguous, on the right device): no
     validation (allocate's per-call host cost; user tensors go through _lib.ptr)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _tensor_rec(t):
+    """What a cache derived from tensor `t` records of it: the tensor OBJECT, held weakly (the cache must not
+    keep a replaced graph's memory alive), and its version counter.  Never its address: the caching allocator
+    hands a freed block to the next tensor of that size, and a new tensor starts at version 0 again."""
+    return (weakref.ref(t), t._version)
+
+
+def _same_tensor(rec, t) -> bool:
+    """`t` is the very tensor object, at the same version, that `rec` (_tensor_rec) recorded.  False for
+    another object over the same memory (a .data alias, a new tensor at a recycled address), after an
+    in-place write, and once the recorded tensor is gone (a dead reference matches nothing)."""
+    return rec is not None and t is not None and rec[0]() is t and rec[1] == t._version
 
 
 def take_rows(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -360,6 +375,7 @@ class Swarm:
                                          _lib.stream()))
         self.row_ptr, self.col = row_ptr, col[: ne.value]
         self._hear = None  # a radius graph is symmetric: its own transpose
+        self._c16 = self._rp64 = None  # (their keys would miss anyway: frees the old graph's copies now)
         return self
 
     def set_graph(self, row_ptr, col):
@@ -380,6 +396,7 @@ class Swarm:
             rp = new_rp
         self.row_ptr = torch.as_tensor(rp.astype(np.int32), device=self.device)
         self.col = torch.as_tensor(cl.astype(np.int32), device=self.device)
+        self._c16 = self._rp64 = None  # (their keys would miss anyway: frees the old graph's copies now)
         # hearers (transpose) CSR for the protocol's push marks: the same arrays when symmetric
         src = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(rp))
         fwd = np.sort(src * max(self.n, 1) + cl)
@@ -402,10 +419,11 @@ class Swarm:
         used then) or the graph is directed."""
         if self.row_ptr is None or getattr(self, "_hear", None) is not None or not 0 < self.n < (1 << 30):
             return None
-        key = (self.row_ptr.data_ptr(), self.col.data_ptr(), self.row_ptr._version, self.col._version,
-               self.n, self.col.numel())
+        # keyed on the tensor objects (held weakly) and their versions, not on addresses (_tensor_rec)
         cached = getattr(self, "_c16", None)
-        if cached is None or cached[0] != key:
+        if cached is None or not (_same_tensor(cached[0][0], self.row_ptr) and _same_tensor(cached[0][1], self.col)
+                                  and cached[0][2:] == (self.n, self.col.numel())):
+            key = (_tensor_rec(self.row_ptr), _tensor_rec(self.col), self.n, self.col.numel())
             c16 = torch.empty(max(self.col.numel(), 1), dtype=torch.int16, device=self.device)
             with torch.cuda.device(self.device):
                 rc = _lib.lib().swarm_graph_compact(_lib.ctx(), self.n, _lib.ptr(self.row_ptr, torch.int32),
@@ -484,10 +502,9 @@ class Swarm:
         copy of row_ptr (kept while row_ptr is unchanged)."""
         if getattr(self, "_hear", None) is not None:
             raise ValueError("int64 row offsets: symmetric neighbour graphs only (swarm_elect_i64)")
-        key = (self.row_ptr.data_ptr(), self.row_ptr._version, self.n)
         cached = getattr(self, "_rp64", None)
-        if cached is None or cached[0] != key:
-            self._rp64 = cached = (key, self.row_ptr.to(torch.int64))
+        if cached is None or not (_same_tensor(cached[0][0], self.row_ptr) and cached[0][1] == self.n):
+            self._rp64 = cached = ((_tensor_rec(self.row_ptr), self.n), self.row_ptr.to(torch.int64))
         rp64 = cached[1]
         m = {"dense": _lib.ELECT_DENSE, "frontier": _lib.ELECT_FRONTIER}[mode] | (_lib.ELECT_TIMED if timed else 0)
         rounds = ctypes.c_int32(0)
@@ -517,13 +534,16 @@ class Swarm:
 
     # ------------------------------------------------------------------ allocation
     def id_index(self) -> torch.Tensor | None:
-        """id -> storage index table (None if IDs are too sparse for a dense table)."""
-        if self._id_index is None and self.n:
+        """id -> storage index table (None if IDs are too sparse for a dense table); built on first use and
+        again whenever self.ids is replaced or modified in place."""
+        if self.n and (self._id_index is None or not _same_tensor(getattr(self, "_id_index_key", None), self.ids)):
+            self._id_index = None
             span = int(self.ids.max()) + 1
             if span <= 4 * self.n + 1024:
                 t = torch.full((span,), -1, dtype=torch.int32, device=self.device)
                 t[self.ids.long()] = torch.arange(self.n, dtype=torch.int32, device=self.device)
                 self._id_index = t
+                self._id_index_key = _tensor_rec(self.ids)
         return self._id_index
 
     def _indexable(self, mode, claim_thr, u_scale) -> bool:
