@@ -33,6 +33,11 @@
 //                              gathers them, 4 lanes per marked agent with interleaved edges.
 //                              Stamps are dealt in 32-agent blocks over the chunks while rounds
 //                              are busy (balance), in agent order in the tail (stamp_slot)
+//   k_sparse_block<LF_PAIR>    the tail of an election that was given a two-hop index (swarm_elect_pairs): TWO
+//                              rounds per launch, exactly (gather_listed_pair's header has the rule); one
+//                              k_sparse_block<LF_PAIR_MARK> round in front of the first pair marks two-hop rows.
+//                              From there on launches and rounds are counted apart: buffers and stamps follow
+//                              the launch, the counter ring the round
 // Marks are plain byte stores, no atomics: stamp act[v] = stamp_of(t+1) (1..255, never 0, so an
 // unmarked byte never matches), double-buffered by round parity and consumed (zeroed) by the
 // sparse round that reads them.  Leaders alternate by
@@ -500,6 +505,10 @@ __device__ __forceinline__ int group_max(int m) {
     if constexpr (G == 4) {
         m = max(m, __builtin_amdgcn_update_dpp(m, m, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
         m = max(m, __builtin_amdgcn_update_dpp(m, m, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+    } else if constexpr (G == 8) {  // both quads hold their maximum; the half-row mirror brings the other quad's
+        m = max(m, __builtin_amdgcn_update_dpp(m, m, 0xB1, 0xF, 0xF, false));
+        m = max(m, __builtin_amdgcn_update_dpp(m, m, 0x4E, 0xF, 0xF, false));
+        m = max(m, __builtin_amdgcn_update_dpp(m, m, 0x141, 0xF, 0xF, false));  // row_half_mirror
     } else {
 #pragma unroll
         for (int o2 = 1; o2 < G; o2 <<= 1) m = max(m, __shfl_xor(m, o2, 64));
@@ -544,14 +553,18 @@ __device__ __forceinline__ int wave_excl_scan(int c, int &total) {
 // to be another lane's -- one register across group_max, where the values kept live, or folded into
 // a mask after it, spill.  One-pass rows of symmetric graphs only; the other rows mark every
 // neighbour, a superset.
-template <typename Off, int G, int K, bool DIR, bool PRUNE, typename CT>
+// M2 (the switch-over round in front of the pair launches, header of gather_listed_pair): a riser marks its
+// whole two-hop row rp2 / c2 instead, unpruned.
+template <typename Off, int G, int K, bool DIR, bool PRUNE, bool M2, typename CT>
 __device__ __forceinline__ void gather_listed(const Off *__restrict__ rp, CT cols,
                                               const Off *__restrict__ hrp, const int32_t *__restrict__ hcol,
                                               const int32_t *__restrict__ P, int32_t *__restrict__ Q,
                                               uint8_t *__restrict__ aw, const StampMap &sm, uint8_t sw,
                                               const int *lst, int total, int first, int step, int64_t c_lo,
                                               int64_t n_count,
-                                              long long &my_chg, int &my_act, int &my_edges) {
+                                              long long &my_chg, int &my_act, int &my_edges,
+                                              const int32_t *__restrict__ rp2 = nullptr,
+                                              const int16_t *__restrict__ c2 = nullptr) {
     const int lane = threadIdx.x & 63, sub = lane & (G - 1);
     using Ix = Off;  // 32-bit offsets in the int32-CSR instantiation (host: < 2^30 agents and edges)
     if (first >= total) return;
@@ -612,7 +625,9 @@ __device__ __forceinline__ void gather_listed(const Off *__restrict__ rp, CT col
         if (valid && sub == 0) st4(Q, Ix(v), m);
         if (up) {
             if (sub == 0) aw[stamp_slot(sm, v)] = sw;
-            if (DIR) {  // the agents that hear v
+            if constexpr (M2) {  // everything within two hops
+                mark_row<int32_t>(aw, sm, Col16{c2}, v & ~63, rp2[v] + sub, rp2[v + 1], G, sw);
+            } else if (DIR) {  // the agents that hear v
                 mark_row<Off>(aw, sm, Col32{hcol}, 0, hrp[v] + sub, hrp[v + 1], Off(G), sw);
             } else if (e - b <= G * K) {  // one pass: c[] still holds this lane's edges (top: those at m)
 #pragma unroll
@@ -628,6 +643,96 @@ __device__ __forceinline__ void gather_listed(const Off *__restrict__ rp, CT col
             my_edges += int(e - b);
         }
     }
+}
+
+// ------------------------------------------------------------------ pair rounds
+// Two synchronous rounds in one launch ("pair rounds").  N[v]: v and its neighbours, N2[v]: the
+// same within two hops, L_t: the state after round t.  L_{t+1}(v) = max of L_t over N[v] and L_{t+2}(v) = max of
+// L_t over N2[v], so a listed agent computes both from the one buffer that holds L_t -- through its row of the
+// two-hop index rp2 / c2 (swarm_graph_pairs_*: v's CSR row first, in CSR order, then the agents at exactly two
+// hops; 16-bit columns as Col16's).
+// Who must be listed: if L_{t+2}(v) > L_t(v), an agent that rose in round t lies in N2[v].  (Take x in N2[v]
+// with L_t(x) > L_t(v) on a path v-u-x.  If L_t(u) > L_t(v), u rose in round t: otherwise v would have taken
+// L_{t-1}(u) = L_t(u) in round t.  If L_t(u) <= L_t(v) < L_t(x), x rose in round t: otherwise u would hold at
+// least L_{t-1}(x) = L_t(x).)  So the launch of rounds (t+1, t+2) reads P = L_t, writes Q (which holds L_{t-2},
+// or L_{t-1} behind the switch-over round) and for each listed v, with m1 / m2 the maxima over N[v] / N2[v]:
+//   Q[v] = m2;  round t+1 counts v if m1 > P[v], round t+2 if m2 > m1;
+//   v marks itself if m2 > P[v] (Q differs from L_{t+2} only on agents that rose in t-1 .. t+2: all listed);
+//   v marks all of N2[v] if m2 > m1 (it rose in round t+2: covers every riser of t+3 and t+4).
+// The single round in front of the first pair marks its risers' N2 rows (gather_listed<M2>); a single round
+// behind a pair needs nothing (the pair's marks are a superset of a single round's).
+// my_chg1 / my_chg2: risers of the first / second round; my_act / my_edges: listed agents and pair-row entries.
+template <int G, int K>
+__device__ __forceinline__ void gather_listed_pair(const int32_t *__restrict__ rp, const int32_t *__restrict__ rp2,
+                                                   Col16 c2, const int32_t *__restrict__ P, int32_t *__restrict__ Q,
+                                                   uint8_t *__restrict__ aw, const StampMap &sm, uint8_t sw,
+                                                   const int *lst, int total, int first, int step, int64_t c_lo,
+                                                   int64_t n_count, long long &my_chg1, long long &my_chg2,
+                                                   int &my_act, int &my_edges) {
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1);
+    if (first >= total) return;
+    // pipelined as gather_listed: the next pass's agent, bounds, degree and own leader under this pass
+    int32_t nv = lst[first + lane / G < total ? first + lane / G : total - 1];
+    int32_t nb = ld4(rp2, nv), ne = ld4(rp2, nv + 1);
+    int32_t nd = ld4(rp, nv + 1) - ld4(rp, nv);
+    int nown = ld4(P, nv);
+    for (int base = first; base < total; base += step) {
+        const bool valid = base + lane / G < total;
+        const int32_t v = nv, b = nb, e = ne, d = nd;
+        const int own = nown;
+        {
+            const int i2 = base + step + lane / G;
+            nv = lst[i2 < total ? i2 : total - 1];
+            nb = ld4(rp2, nv);
+            ne = ld4(rp2, nv + 1);
+            nd = ld4(rp, nv + 1) - ld4(rp, nv);
+            nown = ld4(P, nv);
+        }
+        int m1 = own, m2 = own;
+        for (int32_t k = b + sub; k < e; k += G * K) {
+            int c[K], val[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) c[j] = c2.at32((k + G * j < e) ? k + G * j : e - 1, v & ~63);
+#pragma unroll
+            for (int j = 0; j < K; ++j) val[j] = ld4(P, c[j]);
+#pragma unroll
+            for (int j = 0; j < K; ++j) {  // entry k - b + G * j of the row: a neighbour iff below the degree
+                m2 = max(m2, val[j]);      // (a clamped slot repeats the last entry, at an index >= e - b >= d)
+                if (k - b + G * j < d) m1 = max(m1, val[j]);
+            }
+        }
+        m1 = group_max<G>(m1);
+        m2 = group_max<G>(m2);
+        const bool up1 = valid && m1 > own, up2 = valid && m2 > m1;
+        if (valid && sub == 0) {
+            st4(Q, v, m2);
+            if (m2 > own) aw[stamp_slot(sm, v)] = sw;
+            my_act += 1;
+            my_edges += e - b;
+        }
+        if (up2) mark_row<int32_t>(aw, sm, c2, v & ~63, b + sub, e, G, sw);
+        my_chg1 += __popcll(__ballot(up1 && sub == 0 && v >= c_lo && v < n_count));
+        my_chg2 += __popcll(__ballot(up2 && sub == 0 && v >= c_lo && v < n_count));
+    }
+}
+
+// The pair launch's bookkeeping, by its LAST workgroup (t: the first round of the pair): the totals of the
+// previous launch's rounds published (t-1 and, had it been a pair, t-2: published again otherwise, the same
+// value) and the slots of rounds t + kRing/2 and t + 1 + kRing/2 recycled.
+__device__ __forceinline__ void bookkeeping_last_pair(unsigned long long *ring, unsigned long long *tot, int t,
+                                                      uint32_t ng) {
+    if (blockIdx.x != ng - 1) return;
+    if (tot && threadIdx.x < 2 * kWave) {
+        const int r = t - 1 - int(threadIdx.x >> 6);
+        if (r >= 1) {
+            unsigned long long v = *slot(ring, r, C_CHG, threadIdx.x & 63);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            if ((threadIdx.x & 63) == 0) tot[r % kRing] = v;
+        }
+    }
+    for (int i = threadIdx.x; i < 2 * kCounters * kShards; i += kBlock)
+        *slot(ring, t + kRing / 2 + i / (kCounters * kShards), (i / kShards) % kCounters, i % kShards) = 0;
 }
 
 // S stamps per thread as one word: 8 (uint2, 2 048-agent chunks) or 2 (uint16, 512-agent chunks:
@@ -678,6 +783,12 @@ constexpr unsigned LF_VOTE = 2u;         // SWARM_LIST_VOTE: a wave none of whos
 constexpr unsigned LF_ATOMIC = 4u;       // SWARM_LIST_ATOMIC: waves reserve list slices with one LDS add; one barrier
 constexpr unsigned LF_FLUSH_VOTE = 8u;   // SWARM_FLUSH_VOTE: a wave that gathered nothing skips its counter sums
 constexpr unsigned LF_FLUSH_WAVE = 16u;  // SWARM_FLUSH_WAVE: counters added per wave, no LDS reduction or barrier
+// Not list-phase levers, but carried by the same template argument so that every former instantiation keeps
+// its name and code: the two forms of the pair rounds (gather_listed_pair's header).  The host adds one of
+// them to the default list mask only; such a launch takes its write stamp from bits 8-15 of `flags` (stamps
+// follow the launch counter, the kernel's t the round).
+constexpr unsigned LF_PAIR = 32u;        // rounds t and t + 1 in this launch, through the two-hop index
+constexpr unsigned LF_PAIR_MARK = 64u;   // a single round whose risers mark their two-hop rows (the switch-over)
 constexpr unsigned kListAll = 31u;
 constexpr unsigned kListDefault = LF_VOTE | LF_ATOMIC;  // by the A/B rule (DESIGN_LOG.md r15)
 #ifndef SWARM_LIST_EXTRA  // one more combination for an A/B build (tools/build_variant.sh NAME "-DSWARM_LIST_EXTRA=5")
@@ -735,6 +846,8 @@ struct SparseRest {
     CT cols;
     const Off *hrp;                   // DIR: who hears each agent
     const int32_t *hcol;
+    const int32_t *rp2;               // LF_PAIR / LF_PAIR_MARK: the two-hop index (last: no former field moves)
+    const int16_t *c2;
 };
 
 // A wave-uniform 8-byte word no thread of this kernel writes, read with a scalar load (the scalar cache
@@ -822,8 +935,12 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
     const CT cols = a.cols;
     const Off *__restrict__ hrp = a.hrp;
     const int32_t *__restrict__ hcol = a.hcol;
-    const uint8_t sw = stamp_of(t + 1);
+    constexpr bool PAIR = (LF & LF_PAIR) != 0, PAIR_MARK = (LF & LF_PAIR_MARK) != 0;
+    static_assert(!(PAIR || PAIR_MARK) || (sizeof(Off) == 4 && !DIR && std::is_same_v<CT, Col16>),
+                  "pair rounds: symmetric int32 CSR with unescaped 16-bit columns");
+    const uint8_t sw = (PAIR || PAIR_MARK) ? uint8_t(flags >> 8) : stamp_of(t + 1);
     const int64_t n = a.n_rows;
+    [[maybe_unused]] long long my_chg1 = 0;  // PAIR: risers of round t (my_chg: of round t + 1)
     long long my_chg = 0;
     int my_act = 0, my_edges = 0;
     const int j0 = threadIdx.x * S;  // this thread's S slots: consecutive agents of one block
@@ -956,8 +1073,13 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
 #endif
             listed = listed + total < kListCap ? listed + total : kListCap;
             if (listed < kListCap) break;  // everything fitted
-            gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
-                                          kBlock / G, a.c_lo, a.n_count, my_chg, my_act, my_edges);
+            if constexpr (PAIR)
+                gather_listed_pair<G, K>(rp, a.rp2, Col16{a.c2}, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
+                                         kBlock / G, a.c_lo, a.n_count, my_chg1, my_chg, my_act, my_edges);
+            else
+                gather_listed<Off, G, K, DIR, PRUNE, PAIR_MARK>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed,
+                                                                wid * (64 / G), kBlock / G, a.c_lo, a.n_count, my_chg,
+                                                                my_act, my_edges, a.rp2, a.c2);
             listed = 0;
             __syncthreads();  // the list is reused
         }
@@ -971,15 +1093,30 @@ __global__ __launch_bounds__(kBlock, sizeof(Off) == 4 ? 8 : 6) void k_sparse_blo
 #ifdef SWARM_PHASES
     ph_listed = wall_clock64();
 #endif
-    if (listed > 0)
-        gather_listed<Off, G, K, DIR, PRUNE>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
-                                      kBlock / G, a.c_lo, a.n_count, my_chg, my_act, my_edges);
+    if (listed > 0) {
+        if constexpr (PAIR)
+            gather_listed_pair<G, K>(rp, a.rp2, Col16{a.c2}, P, Q, aw, a.wsm, sw, s_list, listed, wid * (64 / G),
+                                     kBlock / G, a.c_lo, a.n_count, my_chg1, my_chg, my_act, my_edges);
+        else
+            gather_listed<Off, G, K, DIR, PRUNE, PAIR_MARK>(rp, cols, hrp, hcol, P, Q, aw, a.wsm, sw, s_list, listed,
+                                                            wid * (64 / G), kBlock / G, a.c_lo, a.n_count, my_chg,
+                                                            my_act, my_edges, a.rp2, a.c2);
+    }
 #ifdef SWARM_PHASES
     ph_gathered = wall_clock64() + (my_chg & 0);
 #endif
     // (behind the workgroup's own round: in front of it the stamp words it holds in flight were spilled)
-    bookkeeping_last(a.ring, a.tot, t, ng);
-    flush_counts<LF>(a.ring, t, my_chg, my_act, my_edges, s_red);
+    if constexpr (PAIR) {
+        // the first round's risers per wave (wave-uniform: ballot counts); the listed agents, the entries and
+        // the second round's risers go to round t + 1's slots
+        bookkeeping_last_pair(a.ring, a.tot, t, ng);
+        if (lane == 0 && my_chg1)
+            atomicAdd(slot(a.ring, t, C_CHG, blockIdx.x & (kShards - 1)), (unsigned long long)my_chg1);
+        flush_counts<LF>(a.ring, t + 1, my_chg, my_act, my_edges, s_red);
+    } else {
+        bookkeeping_last(a.ring, a.tot, t, ng);
+        flush_counts<LF>(a.ring, t, my_chg, my_act, my_edges, s_red);
+    }
 #ifdef SWARM_PHASES
     if (threadIdx.x == 0 && blockIdx.x < 8192) {
         g_phase[blockIdx.x * 8 + 0] = ph_t0;
@@ -1437,7 +1574,16 @@ struct Tuning {
     int flush_vote;            // SWARM_FLUSH_VOTE: a wave that gathered nothing skips its counter sums
     int flush_wave;            // SWARM_FLUSH_WAVE: per-wave counter adds in place of the LDS reduction
     unsigned list_mask = 0;    // the LF_ bits of the five above
+    // Pair rounds ("pair rounds"): elections given a two-hop index (swarm_elect_pairs) switch to
+    // two rounds per launch once the last read round changed fewer agents than this
+    double pair_below = -1.0;  // SWARM_PAIR_BELOW (changes per round; -1: 8 x sparse_blocks = 16 384, eight risers
+                               // per resident workgroup: measured best at 100k, 1M and 10M agents, where 8e-4 x
+                               // agents, the stamp layout's switch, starts the pairs ~150 rounds late at 10M)
+    int pair_lanes = 8;        // SWARM_PAIR_LANES: lanes per listed agent in a pair launch (8: a ~50-entry row in
+                               // one pass of 8 loads per lane; 4: two passes, 0.3-0.4 ms slower at 10M)
     Tuning() {
+        if (const char *pb = getenv("SWARM_PAIR_BELOW")) pair_below = atof(pb);
+        pair_lanes = env_int("SWARM_PAIR_LANES", 8) == 4 ? 4 : 8;
         list_fast = env_int("SWARM_LIST_FAST", (kListDefault & LF_FAST) != 0);
         list_vote = env_int("SWARM_LIST_VOTE", (kListDefault & LF_VOTE) != 0);
         list_atomic = env_int("SWARM_LIST_ATOMIC", (kListDefault & LF_ATOMIC) != 0);
@@ -1606,54 +1752,99 @@ RoundKind plan_round(int t) {
     return RK_SPARSE;
 }
 
+// A launch of an election that runs pair rounds (elect_impl).  Once a launch has covered two rounds the launch
+// counter lc lags the round: the leader buffers, the stamp parity, the stamp value and the stamp clears follow
+// lc, the counter ring follows the round t.  NULL: lc = t, guard_round = t - 2, form PF_SINGLE.
+enum PairForm { PF_SINGLE = 0, PF_MARK = 1, PF_PAIR = 2 };
+struct RoundPlan {
+    int lc;              // this launch's number (1-based)
+    int guard_round;     // the last round of launch lc - 2, whose total the launch before this one published
+    PairForm form;       // PF_MARK: a single round that marks two-hop rows; PF_PAIR: rounds t and t + 1
+    int lanes;           // PF_PAIR: lanes per listed agent (4 or 8)
+    const int32_t *rp2;  // the two-hop index (PF_MARK, PF_PAIR)
+    const int16_t *c2;
+};
+
 // One k_sparse_block launch: the leading arguments resolved here from the frontier and the round.
-template <typename Off, int S, bool DIR, typename CT, bool PRUNE, unsigned LF>
+template <typename Off, int S, bool DIR, typename CT, bool PRUNE, unsigned LF, int G = kG>
 void launch_sparse_lf(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
-                      const int32_t *hcol, hipStream_t s) {
+                      const int32_t *hcol, hipStream_t s, const RoundPlan *pl = nullptr) {
     const unsigned grid = grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks));
-    const SparseRest<Off, CT> a{f.L[t & 1], f.act[(t + 1) & 1], f.ring, f.tot, f.n_rows, f.c_lo, f.n_count,
-                                f.sm,       f.wsm,              cols,   hrp,   hcol};
-    const unsigned long long *gw = (guard && t > 2) ? f.tot + (t - 2) % kRing : nullptr;
+    const int lc = pl ? pl->lc : t, gr = pl ? pl->guard_round : t - 2;
+    const SparseRest<Off, CT> a{f.L[lc & 1], f.act[(lc + 1) & 1], f.ring, f.tot, f.n_rows, f.c_lo, f.n_count,
+                                f.sm,        f.wsm,               cols,   hrp,   hcol,     pl ? pl->rp2 : nullptr,
+                                pl ? pl->c2 : nullptr};
+    const unsigned long long *gw = (guard && gr > 0) ? f.tot + gr % kRing : nullptr;
     if (!tuning().guard_late) flags |= SF_GUARD_EARLY;
-    hipLaunchKernelGGL((k_sparse_block<Off, S, DIR, CT, kG, kKs, PRUNE, LF>), dim3(grid), dim3(kBlock), 0, s,
-                       f.act[t & 1], gw, static_cast<const int32_t *>(f.L[(t - 1) & 1]), rp, uint32_t(f.sm.M),
-                       uint32_t(grid), t, unsigned(stamp_of(t)) * 0x01010101u, flags, a);
+    if (LF & (LF_PAIR | LF_PAIR_MARK)) flags |= unsigned(stamp_of(lc + 1)) << 8;
+    hipLaunchKernelGGL((k_sparse_block<Off, S, DIR, CT, G, kKs, PRUNE, LF>), dim3(grid), dim3(kBlock), 0, s,
+                       f.act[lc & 1], gw, static_cast<const int32_t *>(f.L[(lc - 1) & 1]), rp, uint32_t(f.sm.M),
+                       uint32_t(grid), t, unsigned(stamp_of(lc)) * 0x01010101u, flags, a);
+}
+
+// The two forms of the pair rounds: int32 CSR, unescaped 16-bit columns, the default list mask.
+template <int S>
+void launch_sparse_pairform(const int32_t *rp, Col16 cols, const Frontier &f, int t, int guard, unsigned flags,
+                            hipStream_t s, const RoundPlan &pl) {
+    if (pl.form == PF_MARK)
+        launch_sparse_lf<int32_t, S, false, Col16, false, kListDefault | LF_PAIR_MARK>(rp, cols, f, t, guard, flags,
+                                                                                       nullptr, nullptr, s, &pl);
+    else if (pl.lanes == 8)
+        launch_sparse_lf<int32_t, S, false, Col16, false, kListDefault | LF_PAIR, 8>(rp, cols, f, t, guard, flags,
+                                                                                     nullptr, nullptr, s, &pl);
+    else
+        launch_sparse_lf<int32_t, S, false, Col16, false, kListDefault | LF_PAIR, 4>(rp, cols, f, t, guard, flags,
+                                                                                     nullptr, nullptr, s, &pl);
 }
 
 // The kernel of the process's list-phase levers (launch_frontier_round has checked that it is compiled).
 template <typename Off, int S, bool DIR, typename CT, bool PRUNE>
 void launch_sparse(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
-                   const int32_t *hcol, hipStream_t s) {
+                   const int32_t *hcol, hipStream_t s, const RoundPlan *pl = nullptr) {
     const unsigned m = tuning().list_mask;
     if (m == kListDefault)
-        launch_sparse_lf<Off, S, DIR, CT, PRUNE, kListDefault>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, kListDefault>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
     else if (m == 0u)
-        launch_sparse_lf<Off, S, DIR, CT, PRUNE, 0u>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, 0u>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
     else if (m == kListAll)
-        launch_sparse_lf<Off, S, DIR, CT, PRUNE, kListAll>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, kListAll>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
     else
-        launch_sparse_lf<Off, S, DIR, CT, PRUNE, unsigned(SWARM_LIST_EXTRA)>(rp, cols, f, t, guard, flags, hrp, hcol, s);
+        launch_sparse_lf<Off, S, DIR, CT, PRUNE, unsigned(SWARM_LIST_EXTRA)>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
 }
 
 // The sparse round of a symmetric graph: chunk size and column type from the frontier, PRUNE from
 // SWARM_MARK_PRUNE.
 template <typename Off, bool PRUNE>
 int launch_sparse_round(const Off *rp, const int32_t *col, const Frontier &f, int t, int guard, unsigned flags,
-                        hipStream_t s) {
+                        hipStream_t s, const RoundPlan *pl = nullptr) {
     const bool small = f.sm.cshift == 9;  // small swarm: 512-agent chunks, 4x the workgroups
     const Col32 c32{col};
+    if (pl && pl->form != PF_SINGLE) {
+        if constexpr (sizeof(Off) == 4) {
+            SW_ARG(f.c16 && !f.c16_esc && pl->rp2 && pl->c2 && tuning().list_mask == kListDefault,
+                   "pair rounds need the unescaped 16-bit columns, the two-hop index and the default list levers");
+            if (small)
+                launch_sparse_pairform<2>(rp, Col16{f.c16}, f, t, guard, flags, s, *pl);
+            else
+                launch_sparse_pairform<kScan>(rp, Col16{f.c16}, f, t, guard, flags, s, *pl);
+            SW_LAUNCHED();
+            return SWARM_OK;
+        } else {
+            SW_ARG(false, "pair rounds: int32 row offsets only");
+        }
+    }
     if (f.c16 && f.c16_esc && small)
-        launch_sparse<Off, 2, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s);
+        launch_sparse<Off, 2, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s, pl);
     else if (f.c16 && f.c16_esc)
-        launch_sparse<Off, kScan, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s);
+        launch_sparse<Off, kScan, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s, pl);
     else if (f.c16 && small)
-        launch_sparse<Off, 2, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s);
+        launch_sparse<Off, 2, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s, pl);
     else if (f.c16)
-        launch_sparse<Off, kScan, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s);
+        launch_sparse<Off, kScan, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s, pl);
     else if (small)
-        launch_sparse<Off, 2, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s);
+        launch_sparse<Off, 2, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s, pl);
     else
-        launch_sparse<Off, kScan, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s);
+        launch_sparse<Off, kScan, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s, pl);
     SW_LAUNCHED();
     return SWARM_OK;
 }
@@ -1669,7 +1860,8 @@ bool clear_due(int t) { return t > 2 && ((t - 1) & 255) < 2; }
 template <typename Off>
 int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, int t, RoundKind k, int guard,
                           hipStream_t s, const Off *hrp = nullptr, const int32_t *hcol = nullptr,
-                          int *cleared_for = nullptr) {
+                          int *cleared_for = nullptr, const RoundPlan *pl = nullptr) {
+    const int lc = pl ? pl->lc : t;  // the stamp buffers and their clears follow the launch counter
     if (k == RK_DENSE || k == RK_DENSE_MARK)
         return launch_dense_round<Off>(rp, col, f.L[(t - 1) & 1], f.L[t & 1], f.n_rows, f.c_lo, f.n_count, f.ring,
                                        f.tot,
@@ -1678,15 +1870,15 @@ int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, 
     // The clear: done by round t-1 where that was a sparse round launched here with SF_CLEAR (it zeroed
     // every stamp word behind its load), by a memset otherwise -- after a dense round, the one-workgroup
     // tail, or at the first round of a stepper run.
-    if (clear_due(t) && !(cleared_for && *cleared_for == t))
-        SW_HIP(hipMemsetAsync(f.act[(t + 1) & 1], 0, act_bytes(f.n_all), s));
+    if (clear_due(lc) && !(cleared_for && *cleared_for == lc))
+        SW_HIP(hipMemsetAsync(f.act[(lc + 1) & 1], 0, act_bytes(f.n_all), s));
     SW_ARG(list_mask_compiled(tuning().list_mask),
            "SWARM_LIST_* / SWARM_FLUSH_*: this combination of list-phase levers is not compiled (none, all, the "
            "default, or -DSWARM_LIST_EXTRA=mask)");
     unsigned flags = 0;
-    if (tuning().clear_inline && cleared_for && clear_due(t + 1)) {  // this round is that buffer's last reader
+    if (tuning().clear_inline && cleared_for && clear_due(lc + 1)) {  // this round is that buffer's last reader
         flags |= SF_CLEAR;
-        *cleared_for = t + 1;
+        *cleared_for = lc + 1;
     }
     if (hrp) {  // directed: the marks go to hearers, whose leaders the riser did not read -- never pruned
         if (f.sm.cshift == 9)
@@ -1696,8 +1888,8 @@ int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, 
         SW_LAUNCHED();
         return SWARM_OK;
     }
-    return tuning().mark_prune ? launch_sparse_round<Off, true>(rp, col, f, t, guard, flags, s)
-                               : launch_sparse_round<Off, false>(rp, col, f, t, guard, flags, s);
+    return tuning().mark_prune ? launch_sparse_round<Off, true>(rp, col, f, t, guard, flags, s, pl)
+                               : launch_sparse_round<Off, false>(rp, col, f, t, guard, flags, s, pl);
 }
 
 // Algorithmic HBM bytes of one round:
@@ -1767,7 +1959,7 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
                int32_t *leader, uint8_t *state, int32_t max_rounds, int32_t mode,
                int32_t *rounds_exec, int64_t *changes_host, swarm_elect_stats *st,
                void *stream, const Off *hrp = nullptr, const int32_t *hcol = nullptr,
-               const int16_t *c16 = nullptr) {
+               const int16_t *c16 = nullptr, const int32_t *rp2 = nullptr, const int16_t *c2 = nullptr) {
     SW_ARG(ctx != nullptr, "ctx is NULL");
     SW_ARG(n >= 0, "n < 0");
     SW_ARG(n < (int64_t(1) << 31), "n must be < 2^31");
@@ -1941,7 +2133,18 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         consume(upto);
         return SWARM_OK;
     };
-    int cleared_for = 0;  // the round whose stamp clear the round before it did in its own launch
+    int cleared_for = 0;  // the launch whose stamp clear the launch before it did in its own launch
+    // Pair rounds (gather_listed_pair's header): with a two-hop index, once the last read round changed fewer
+    // than pair_below agents, one single round marks two-hop rows (PF_MARK) and every launch behind it covers
+    // two rounds (PF_PAIR) -- a single one only where one round is left before max_rounds.  lc counts launches,
+    // lend[i] is the last round of launch i (lend[0] = 0): buffers and stamps follow lc, counters the round.
+    const bool pair_ok = rp2 && c2 && c16 && !hrp && sizeof(Off) == 4 && mode == SWARM_ELECT_FRONTIER && !rlog &&
+                         tuning().tail_wg == 0 && tuning().list_mask == kListDefault;
+    const double pair_below = tuning().pair_below >= 0 ? tuning().pair_below : 8.0 * tuning().sparse_blocks;
+    bool pair_mode = false;
+    int lc = 0;
+    int64_t pair_launches = 0;
+    std::vector<int> lend(1, 0);
     int64_t tail_retry_below = INT64_MAX;  // the tail did not start: retry once the changes halve
     // One-workgroup tail from round launched + 1: drain, collect the marked agents, run k_tail_wg, read its
     // rounds' counters.  Leaves launched / rd_map where the frontier rounds go on.
@@ -1999,6 +2202,7 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
                         double(hc[2 * (r - t0 + 1)] - hc[2 * (r - t0)]) / 100.0);
         }
         launched = last;
+        while (lc < launched) lend.push_back(++lc);  // (no pair rounds with the tail: a launch per round)
         if (int rc2 = read_rounds(last)) return rc2;
         rd_map = ag_map;  // the hand-back marks (if the run goes on)
         batch = 8;
@@ -2017,7 +2221,9 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         // between every launch would add their own cost to each round (rocprof's per-dispatch
         // durations are the reference for this figure)
         int seg_n = 0;  // sparse launches inside this batch's segment
-        for (int r = t; r <= tend; ++r) {
+        int last_end = launched;  // the last round launched (a batch's last pair may end one round past tend)
+        for (int r = t, step = 1; r <= tend; r += step) {
+            step = 1;
             const bool sparse = mode == SWARM_ELECT_FRONTIER && plan_round(r) == RK_SPARSE;
             const bool seg = timed && sparse && !rlog;
             if (seg && seg_n++ == 0) SW_HIP(hipEventRecord(ev[2 * kMaxBatch], s));
@@ -2039,20 +2245,36 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
                 // order once they are sparse (locality of the few gathers)
                 f.sm = rd_map;
                 f.wsm = (hist.empty() || hist.back() >= il_min) ? il_map : ag_map;
-                rc = launch_frontier_round<Off>(rp, col, f, r, kinds[r - t], 1, s, hrp, hcol, &cleared_for);
+                RoundPlan pl{lc + 1, lc >= 2 ? lend[lc - 1] : 0, PF_SINGLE, tuning().pair_lanes, rp2, c2};
+                if (pair_ok && kinds[r - t] == RK_SPARSE) {
+                    if (!pair_mode && !hist.empty() && double(hist.back()) < pair_below) {
+                        pl.form = PF_MARK;
+                        pair_mode = true;
+                    } else if (pair_mode && r + 1 <= max_rounds) {
+                        pl.form = PF_PAIR;
+                        step = 2;
+                        ++pair_launches;
+                        if (r + 1 - t < kMaxBatch) kinds[r + 1 - t] = RK_SPARSE;
+                    }
+                }
+                rc = launch_frontier_round<Off>(rp, col, f, r, kinds[r - t], 1, s, hrp, hcol, &cleared_for,
+                                                pair_ok ? &pl : nullptr);
                 rd_map = f.wsm;
             }
             if (rc) return rc;
+            ++lc;
+            last_end = r + step - 1;
+            lend.push_back(last_end);
             if (e2) SW_HIP(hipEventRecord(e2[1], s));
-            if (r == tread && (rc = enqueue_read())) return rc;
+            if (tread >= r && tread <= last_end && (rc = enqueue_read())) return rc;
         }
         if (seg_n) SW_HIP(hipEventRecord(ev[2 * kMaxBatch + 1], s));
-        launched = std::max(launched, tend);
+        launched = std::max(launched, last_end);
         if ((rc = wait_mapped_word(h_epoch, ep_tag | ep, s, "election read-back"))) return rc;
         if (timed) {  // kLook == 0: this batch's rounds are exactly the rounds read
             SW_HIP(hipStreamSynchronize(s));
             for (int r = t; r <= tend; ++r) {  // every launched round's kernel time (rocprof's view)
-                if (seg_n && kinds[r - t] == RK_SPARSE) continue;  // in the segment
+                if (seg_n && kinds[r - t] == RK_SPARSE) continue;  // in the segment (a pair: both its rounds)
                 float x = 0;
                 SW_HIP(hipEventElapsedTime(&x, ev[2 * (r - t)], ev[2 * (r - t) + 1]));
                 k_ms += x;
@@ -2075,7 +2297,20 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         consume(tread);
         // a batch spans at most kRing/2 rounds of counter slots, look-ahead included (bookkeeping
         // recycles the slot of round t - kRing/2 in round t)
-        batch = next_round_batch(hist.data(), hist.size(), batch, kMaxBatch - kLook);
+        // (pair rounds: one round of room for the pair that ends past its batch)
+        batch = next_round_batch(hist.data(), hist.size(), batch, kMaxBatch - kLook - (pair_ok ? 2 : 0));
+        // The switch to pair rounds happens at a batch's first round: a batch that is about to cross pair_below
+        // ends where the linear trend of the last 32 rounds crosses it (8 rounds at the least), and within a
+        // quarter above it (the curve is flat and noisy there at 10M agents: 20 changes per round of slope)
+        // batches are 16 rounds, so that the pairs do not start a long batch late.
+        if (pair_ok && !pair_mode && hist.size() >= 32 && double(hist.back()) >= pair_below) {
+            const double slope = double(hist[hist.size() - 32] - hist.back()) / 31.0;
+            if (slope > 0) {
+                const double rem = 1.1 * (double(hist.back()) - pair_below) / slope + 2.0;
+                batch = std::min(batch, rem < 8.0 ? 8 : rem > double(kMaxBatch) ? kMaxBatch : int(rem));
+            }
+            if (double(hist.back()) < 1.25 * pair_below) batch = std::min(batch, 16);
+        }
         // the one-workgroup tail (opt-in experiment): once the last read round's risers x 4 fit its list (the
         // marked agents of a tail round are ~3x the previous round's risers at 100k-10M agents; a list that
         // does not fit is caught by the collect), with short batches once that is near, so that the switch
@@ -2089,10 +2324,18 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         }
     }
     const int last = found > 0 ? found : max_rounds;
-    if ((found < 0 && (last & 1)) || (skip_copy && last == 1)) {
-        // after a zero-change round both buffers hold the final state (dense and frontier alike);
-        // otherwise the newest is bufs[last & 1].  (Without the initial copies a run that ends with
-        // round 1 has written bufs[1] only, zero changes or not.)
+    // The newest buffer is bufs[lc & 1] (lc launches were issued).  After a launch whose rounds all changed
+    // nothing both buffers hold the final state (dense and frontier alike).  A pair launch whose first round
+    // changed something and whose second nothing leaves it in the buffer it wrote only; the launch behind it
+    // (not guarded: its guard word is an earlier, non-zero round's) rewrites the other one.  (Without the
+    // initial copies a run that ends with round 1 has written bufs[1] only, zero changes or not.)
+    bool newest_only = found < 0;
+    int lfin = lc;  // the launch that wrote the final state
+    if (found > 0) {
+        lfin = int(std::lower_bound(lend.begin(), lend.end(), found) - lend.begin());
+        newest_only = lfin == lc && lfin >= 1 && lend[lfin - 1] + 1 != found;
+    }
+    if ((newest_only && (lfin & 1)) || (skip_copy && last == 1)) {
         SW_HIP(hipMemcpyAsync(leader, bufs[1], size_t(n) * 4, hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(k_state, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, leader,
@@ -2112,6 +2355,7 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         st->sparse_ms = sp_ms;
         st->sparse_launches = sp_launches;
         st->sparse_bytes = sp_bytes;
+        st->pair_launches = pair_launches;
     }
     return found > 0 ? SWARM_OK : SWARM_NOT_CONVERGED;
 }
@@ -2275,6 +2519,24 @@ int swarm_elect_compact(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const
     return swarm::elect_impl<int32_t>(ctx, n, row_ptr, col, ids, leader, state, max_rounds, mode, rounds_exec,
                                       changes_per_round, stats, stream, nullptr, nullptr,
                                       swarm::tuning().use_c16 ? col16 : nullptr);
+}
+
+int swarm_elect_pairs(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, const int16_t *col16,
+                      const int32_t *rp2, const int16_t *col2, const int32_t *ids, int32_t *leader, uint8_t *state,
+                      int32_t max_rounds, int32_t mode, int32_t *rounds_exec, int64_t *changes_per_round,
+                      swarm_elect_stats *stats, void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr, "ctx is NULL");
+    SW_ARG(col16 && rp2 && col2, "swarm_elect_pairs needs col16, rp2 and col2 (swarm_elect_compact runs without)");
+    // the index is written through (marks) and never checked on the device: only this ctx's own build of it,
+    // from these very arrays, is taken
+    bool known = false;
+    for (const auto &p : ctx->pairs_built)
+        known |= p.rp2 == rp2 && p.col2 == col2 && p.rp == row_ptr && p.col == col && p.n == n;
+    SW_ARG(known, "rp2 / col2 are not swarm_graph_pairs_fill's index of this row_ptr / col on this ctx");
+    return elect_impl<int32_t>(ctx, n, row_ptr, col, ids, leader, state, max_rounds, mode, rounds_exec,
+                               changes_per_round, stats, stream, nullptr, nullptr,
+                               tuning().use_c16 ? col16 : nullptr, rp2, col2);
 }
 
 int swarm_elect_directed(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col,

@@ -185,6 +185,13 @@ struct swarm_ctx {
         int64_t n, e_total;
     };
     std::vector<C16Built> c16_built;
+    struct PairsBuilt {                      // two-hop indexes swarm_graph_pairs_fill last wrote (pairs.hip)
+        const int32_t *rp2;
+        const int16_t *col2;
+        const int32_t *rp, *col;
+        int64_t n;
+    };
+    std::vector<PairsBuilt> pairs_built;
     int step_rd_agent = 0;         // frontier stepper: the marks the next round reads are in agent order
     int step_wr_agent = 0;         // ... and the next round writes its marks in agent order (the tail)
     int step_cleared_for = 0;      // frontier stepper: the round whose stamp clear the round before it has done

@@ -45,7 +45,8 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_obstacle_field_refresh", "swarm_board_create", "swarm_board_info", "swarm_board_read",
            "swarm_board_destroy", "swarm_update_loop_board", "swarm_permute_rows", "swarm_graph_relabel",
            "swarm_resort_plan", "swarm_board_create_moving", "swarm_board_set_velocities", "swarm_board_positions",
-           "swarm_board_refresh", "swarm_board_call_box", "swarm_update_loop_board_moving")
+           "swarm_board_refresh", "swarm_board_call_box", "swarm_update_loop_board_moving",
+           "swarm_graph_pairs_count", "swarm_graph_pairs_fill", "swarm_elect_pairs")
 BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
 BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
 
@@ -115,7 +116,8 @@ class ElectStats(ctypes.Structure):
                 ("gather_ms", ctypes.c_double), ("apply_ms", ctypes.c_double),
                 ("gather_launches", ctypes.c_int64), ("dense_rounds", ctypes.c_int64),
                 ("bytes_total", ctypes.c_double), ("sparse_ms", ctypes.c_double),
-                ("sparse_launches", ctypes.c_int64), ("sparse_bytes", ctypes.c_double)]
+                ("sparse_launches", ctypes.c_int64), ("sparse_bytes", ctypes.c_double),
+                ("pair_launches", ctypes.c_int64)]
 
 
 class AuctionStats(ctypes.Structure):
@@ -182,6 +184,9 @@ def load(path: str = LIB_PATH):
         L.swarm_graph_compact.argtypes = [P, i64, P, P, P, P]
         L.swarm_elect_compact.argtypes = [P, i64, P, P, P, P, P, P, i32, i32, ctypes.POINTER(i32), P, P, P]
         L.swarm_elect_compact_i64.argtypes = [P, i64, P, P, P, P, P, P, i32, i32, ctypes.POINTER(i32), P, P, P]
+        L.swarm_graph_pairs_count.argtypes = [P, i64, P, P, i32, P, P]
+        L.swarm_graph_pairs_fill.argtypes = [P, i64, P, P, P, P, P]
+        L.swarm_elect_pairs.argtypes = [P, i64, P, P, P, P, P, P, P, P, i32, i32, ctypes.POINTER(i32), P, P, P]
         L.swarm_allocate.argtypes = [P, i64, P, P, P, i64, P, P, d, d, d, i32, P, P, P, P, i64,
                                      P, P, P, P]
         L.swarm_utility.argtypes = [P, i64, P, P, P, P, d, P, P]

@@ -62,6 +62,20 @@ def _to(a, dtype, device):
     return torch.as_tensor(a, dtype=dtype, device=device)
 
 
+# Pair rounds (elect.hip, "pair rounds"): the frontier election's tail runs two rounds per launch
+# through a two-hop index of the graph.  Swarms of at least SWARM_PAIR_MIN_AGENTS agents build the index on their
+# first frontier election of a graph version and use it by default (Swarm.elect(pairs=...) overrides).
+# The default is the A/B of tools/elect_ab.py at 1M and 10M agents (DESIGN_LOG.md): PAIR_MIN_AGENTS_DEFAULT.
+PAIR_MIN_AGENTS_DEFAULT = 1_000_000
+# rows longer than this refuse the index (hub rows: a riser's row is walked by 4 or 8 lanes); a degree-16 radius
+# graph's longest two-hop row is ~90
+PAIR_ROW_CAP = 512
+
+
+def _pair_min_agents() -> int:
+    return int(os.environ.get("SWARM_PAIR_MIN_AGENTS", PAIR_MIN_AGENTS_DEFAULT))
+
+
 # SWARM_TRUST_C16=0 (A/B aid): every election re-checks the 16-bit columns on the device
 _TRUST_C16 = _lib.ELECT_TRUST_C16 if os.environ.get("SWARM_TRUST_C16", "1") != "0" else 0
 
@@ -375,7 +389,7 @@ class Swarm:
                                          _lib.stream()))
         self.row_ptr, self.col = row_ptr, col[: ne.value]
         self._hear = None  # a radius graph is symmetric: its own transpose
-        self._c16 = self._rp64 = None  # (their keys would miss anyway: frees the old graph's copies now)
+        self._c16 = self._rp64 = self._pairs = None  # (their keys would miss anyway: frees the old graph's copies now)
         return self
 
     def set_graph(self, row_ptr, col):
@@ -396,7 +410,7 @@ class Swarm:
             rp = new_rp
         self.row_ptr = torch.as_tensor(rp.astype(np.int32), device=self.device)
         self.col = torch.as_tensor(cl.astype(np.int32), device=self.device)
-        self._c16 = self._rp64 = None  # (their keys would miss anyway: frees the old graph's copies now)
+        self._c16 = self._rp64 = self._pairs = None  # (their keys would miss anyway: frees the old graph's copies now)
         # hearers (transpose) CSR for the protocol's push marks: the same arrays when symmetric
         src = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(rp))
         fwd = np.sort(src * max(self.n, 1) + cl)
@@ -436,8 +450,56 @@ class Swarm:
             self._c16 = cached = (key, c16)
         return cached[1]
 
+    def graph_pairs(self):
+        """The two-hop index of the (symmetric) neighbour graph for the election's pair rounds, as (rp2, col2)
+        device tensors (swarm_graph_pairs_count / _fill: row v holds v's CSR row first, then the agents at
+        exactly two hops, as 16-bit deltas from v & ~63), or None when it cannot be had: a directed graph, no
+        edges, a delta that does not fit, a row longer than PAIR_ROW_CAP, 2^31 - 2^20 entries or more, or not
+        enough device memory.  Built on first use and again whenever row_ptr / col are replaced or modified in
+        place (keyed like graph_compact's columns); the refusal is cached too.  last_pairs_build_ms: the wall
+        time of the last build."""
+        if self.row_ptr is None or getattr(self, "_hear", None) is not None or not 0 < self.n < (1 << 30) \
+                or self.n_edges == 0:
+            return None
+        cached = getattr(self, "_pairs", None)
+        if cached is None or not (_same_tensor(cached[0][0], self.row_ptr) and _same_tensor(cached[0][1], self.col)
+                                  and cached[0][2:] == (self.n, self.col.numel())):
+            import time
+            key = (_tensor_rec(self.row_ptr), _tensor_rec(self.col), self.n, self.col.numel())
+            self._pairs = None  # the old index goes before the new one is allocated
+            idx = None
+            L = _lib.lib()
+            t0 = time.perf_counter()
+            with torch.cuda.device(self.device):
+                try:
+                    counts = torch.empty(self.n, dtype=torch.int32, device=self.device)
+                    rc = L.swarm_graph_pairs_count(_lib.ctx(), self.n, _lib.ptr(self.row_ptr, torch.int32),
+                                                   _lib.ptr(self.col, torch.int32), PAIR_ROW_CAP, _lib.ptr(counts),
+                                                   _lib.stream())
+                    if rc != _lib.ERR_RANGE:
+                        _lib.check(rc)
+                        rp2 = torch.zeros(self.n + 1, dtype=torch.int64, device=self.device)
+                        rp2[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+                        total = int(rp2[-1])
+                        del counts
+                        if 0 < total < _C16_EDGE_CAP:
+                            rp2 = rp2.to(torch.int32)
+                            col2 = torch.empty(total, dtype=torch.int16, device=self.device)
+                            rc = L.swarm_graph_pairs_fill(_lib.ctx(), self.n, _lib.ptr(self.row_ptr, torch.int32),
+                                                          _lib.ptr(self.col, torch.int32), _lib.ptr(rp2),
+                                                          _lib.ptr(col2), _lib.stream())
+                            if rc != _lib.ERR_RANGE:
+                                _lib.check(rc)
+                                idx = (rp2, col2)
+                except torch.OutOfMemoryError:  # no room for the index: elect without pair rounds
+                    idx = None
+                torch.cuda.synchronize()
+            self.last_pairs_build_ms = (time.perf_counter() - t0) * 1e3
+            self._pairs = cached = (key, idx)
+        return cached[1]
+
     def elect(self, mode: str = "frontier", max_rounds: int = 1 << 16, timed: bool = False,
-              compact: bool = True, wide: bool | None = None) -> ElectResult:
+              compact: bool = True, wide: bool | None = None, pairs: bool | None = None) -> ElectResult:
         """Contract E2 to convergence on the GPU (swarm_elect_compact with the graph's 16-bit
         columns when they fit; swarm_elect_directed when the neighbour lists are not symmetric).
         timed: per-kernel HIP events.  compact=False: the int32-column entry point swarm_elect
@@ -445,7 +507,11 @@ class Swarm:
         graphs of >= 2^30 edges unless their 16-bit columns fit (swarm_elect_compact then takes up
         to 2^31 - 2^20 edges on 32-bit offsets: C5's 100M agents on one GPU, ~1.6e9), True forces it.
         The 16-bit columns are graph_compact's, rebuilt whenever row_ptr / col change: the call passes
-        SWARM_ELECT_TRUST_C16, so the library skips its device check of them (include/swarm.h)."""
+        SWARM_ELECT_TRUST_C16, so the library skips its device check of them (include/swarm.h).
+        pairs: the frontier election's tail two rounds per launch through graph_pairs()'s index
+        (swarm_elect_pairs; same results).  None: for swarms of at least SWARM_PAIR_MIN_AGENTS agents; True /
+        False force it on / off.  Where the index cannot be had the election runs without (result.pair_launches
+        is 0)."""
         if self.row_ptr is None:
             raise RuntimeError("no neighbour graph: call build_graph() or set_graph()")
         if wide is None:
@@ -465,7 +531,17 @@ class Swarm:
         hear = getattr(self, "_hear", None)
         with torch.cuda.device(self.device):
             c16 = self.graph_compact() if (compact and hear is None) else None
-            if c16 is not None:  # symmetric graph, 16-bit columns
+            if pairs is None:
+                pairs = n >= _pair_min_agents()
+            idx = self.graph_pairs() if (pairs and c16 is not None and mode == "frontier" and _c16_rounds()) else None
+            if idx is not None:  # symmetric graph, 16-bit columns, two-hop index: pair rounds in the tail
+                rc = _lib.check(_lib.lib().swarm_elect_pairs(
+                    _lib.ctx(), n, _lib.ptr(self.row_ptr, torch.int32), _lib.ptr(self.col, torch.int32),
+                    _lib.ptr(c16), _lib.ptr(idx[0], torch.int32), _lib.ptr(idx[1], torch.int16),
+                    _lib.ptr(self.ids, torch.int32), _lib.ptr(self.leader, torch.int32),
+                    _lib.ptr(self.state, torch.uint8), cap, m | _TRUST_C16, ctypes.byref(rounds),
+                    changes.ctypes.data_as(ctypes.c_void_p), ctypes.byref(st), _lib.stream()))
+            elif c16 is not None:  # symmetric graph, 16-bit columns
                 # graph_compact built them on this ctx from the current row_ptr / col (its cache key holds
                 # their versions): the library skips its column check and edge-count read-back
                 rc = _lib.check(_lib.lib().swarm_elect_compact(
@@ -495,6 +571,7 @@ class Swarm:
         res.sparse_ms, res.sparse_launches, res.sparse_bytes = st.sparse_ms, st.sparse_launches, st.sparse_bytes
         res.compact = c16 is not None  # the rounds read the 16-bit columns (2 of the 4 column bytes)
         res.wide = False               # 32-bit row offsets
+        res.pair_launches = st.pair_launches  # launches that ran two rounds (0: no index, or never switched)
         return res
 
     def _elect_wide(self, mode: str, max_rounds: int, timed: bool, compact: bool = True) -> ElectResult:
@@ -530,6 +607,7 @@ class Swarm:
         # col16 only with 32-bit offsets): only the frontier's sparse rounds read the 16-bit ones
         res.compact = c16 is not None and mode == "frontier"
         res.wide = True
+        res.pair_launches = 0
         return res
 
     # ------------------------------------------------------------------ allocation
@@ -1523,7 +1601,7 @@ class Swarm:
             self.row_ptr, self.col = graph
             self._hear = hear
         # everything keyed on the old order
-        self._c16 = self._rp64 = self._again = self._id_index = None
+        self._c16 = self._rp64 = self._pairs = self._again = self._id_index = None
         self._cindex = self._cindex_key = self._cindex_bad = None
         if pos_prev_kept:
             self._pos_prev_key = (self.pos, self.pos._version)

@@ -82,18 +82,19 @@ typedef struct swarm_alloc_stats {
 } swarm_alloc_stats;
 
 typedef struct swarm_elect_stats {
-    int64_t rounds_launched; /* rounds issued (>= rounds_exec; extra ones are no-ops) */
+    int64_t rounds_launched; /* rounds issued (>= rounds_exec; extra ones are no-ops); a pair launch issues two */
     int64_t active_total;    /* agents gathered (DENSE: all; SPARSE: marked), rounds 1..rounds_exec */
     int64_t edges_total;     /* CSR edges visited, summed over rounds 1..rounds_exec */
     int64_t changes_total;   /* leader changes, summed over rounds */
     double gather_ms;        /* SWARM_ELECT_TIMED: device time of every launched round kernel */
     double apply_ms;         /* always 0 (one kernel per round); kept for layout stability */
-    int64_t gather_launches; /* launches behind gather_ms (all launched rounds) */
+    int64_t gather_launches; /* kernel launches behind gather_ms (all launched rounds; a pair launch is one) */
     int64_t dense_rounds;    /* rounds executed as a full DENSE sweep */
     double bytes_total;      /* algorithmic HBM bytes of rounds 1..rounds_exec */
     double sparse_ms;        /* SWARM_ELECT_TIMED: device time of every launched sparse round */
-    int64_t sparse_launches; /* SWARM_ELECT_TIMED: sparse rounds launched (incl. no-ops) */
+    int64_t sparse_launches; /* SWARM_ELECT_TIMED: sparse kernel launches (incl. no-ops; a pair launch is one) */
     double sparse_bytes;     /* algorithmic HBM bytes of the executed sparse rounds */
+    int64_t pair_launches;   /* launches that ran two rounds each (swarm_elect_pairs); 0 elsewhere */
 } swarm_elect_stats;
 
 const char *swarm_last_error(void);
@@ -159,6 +160,38 @@ int swarm_graph_compact_escaped(swarm_ctx *ctx, int64_t n, const int32_t *row_pt
 int swarm_elect_compact(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, const int16_t *col16,
                         const int32_t *ids, int32_t *leader, uint8_t *state, int32_t max_rounds, int32_t mode,
                         int32_t *rounds_exec, int64_t *changes_per_round, swarm_elect_stats *stats, void *stream);
+
+/* The two-hop index of a symmetric int32 CSR, for swarm_elect_pairs (an MI355X layout, no reference
+ * counterpart).  Row v of (rp2, col2) holds v's CSR row first, in CSR order, then every agent at exactly two
+ * hops: no duplicates, never v itself; col2 holds 16-bit deltas from the row's 64-agent base (v & ~63), as
+ * swarm_graph_compact's columns.  Built on the device in two calls, once per graph version -- outside a
+ * steady-state step, as the 16-bit columns and the allocation's cell index are:
+ *   swarm_graph_pairs_count  counts[v] (device, n int32) = row v's length;
+ *   the caller forms rp2 (device, n + 1 int32) = the exclusive prefix sums of counts, allocates col2
+ *   (device, rp2[n] int16), and
+ *   swarm_graph_pairs_fill   writes the rows.
+ * Either call returns SWARM_ERR_RANGE, and the caller then simply elects without pair rounds, when an agent
+ * within two hops lies more than 32767 slots from its row's base (expected for 100M agents on one GPU), when a
+ * row is longer than max_row (hub rows: a pair launch walks a riser's row with 4 or 8 lanes), or when the index
+ * has 2^31 - 2^20 entries or more.  At 10M agents of degree 16 the index has ~0.5 G entries (~1 GB).  The ctx
+ * remembers the index it filled; rebuild it whenever the graph changes.  0 < n < 2^30.  Both synchronise. */
+int swarm_graph_pairs_count(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, int32_t max_row,
+                            int32_t *counts, void *stream);
+int swarm_graph_pairs_fill(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, const int32_t *rp2,
+                           int16_t *col2, void *stream);
+
+/* swarm_elect_compact whose FRONTIER tail runs two synchronous rounds per kernel launch (same election, same
+ * results, same per-round change counts; replaces the same handlers as swarm_elect, agent.py:243-275).  Once a
+ * round has changed fewer than SWARM_PAIR_BELOW agents (default: 16 384, eight per resident workgroup), each launch gathers every listed
+ * agent's two-hop row from the one buffer that holds L_t and writes L_{t+2}: max over N[v] is round t+1's value,
+ * max over the whole row round t+2's ("pair rounds").  rp2 / col2 must be the index this ctx
+ * filled from these row_ptr / col (SWARM_ERR_ARG otherwise); col16 as swarm_elect_compact's.  A single round is
+ * launched where only one is left before max_rounds.  stats->pair_launches counts the two-round launches;
+ * rounds_launched keeps counting rounds.  DENSE mode, SWARM_TAIL_WG and SWARM_ROUND_LOG run without pairs. */
+int swarm_elect_pairs(swarm_ctx *ctx, int64_t n, const int32_t *row_ptr, const int32_t *col, const int16_t *col16,
+                      const int32_t *rp2, const int16_t *col2, const int32_t *ids, int32_t *leader, uint8_t *state,
+                      int32_t max_rounds, int32_t mode, int32_t *rounds_exec, int64_t *changes_per_round,
+                      swarm_elect_stats *stats, void *stream);
 
 /* Same with int64 row offsets: graphs with >= 2^30 edges or agents (the int32-CSR entry points
  * address with 32-bit byte offsets and reject them with SWARM_ERR_ARG; swarm_elect_compact with

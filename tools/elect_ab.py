@@ -1,5 +1,7 @@
 """A/B timing aid: untimed wall time of swarm_elect(FRONTIER) at N agents for one libswarm build.
-Usage: python tools/elect_ab.py LIBNAME [N]   (LIBNAME under swarm_amd/, e.g. libswarm.so)"""
+Usage: python tools/elect_ab.py LIBNAME [N]   (LIBNAME under swarm_amd/, e.g. libswarm.so)
+Pair rounds on against off: SWARM_PAIR_MIN_AGENTS=0 against SWARM_PAIR_MIN_AGENTS=2000000000 (the index is built
+by the warm-up election, outside the timed ones)."""
 import os
 import sys
 import time
@@ -23,6 +25,9 @@ for _ in range(5):
     r = sw.elect()
     torch.cuda.synchronize()
     ts.append(time.perf_counter() - t0)
+idx = sw._pairs[1] if getattr(sw, "_pairs", None) else None  # the two-hop index, when this run built one
+pairs = "" if idx is None else (f" pair_launches {r.pair_launches} index build {sw.last_pairs_build_ms:.1f} ms "
+                                f"{(idx[0].numel() * 4 + idx[1].numel() * 2) / 1e6:.0f} MB")
 print(f"{sys.argv[1]}: n={n} rounds={r.rounds_exec} launched={r.rounds_launched} "
       f"elect ms min {min(ts) * 1e3:.2f} med {sorted(ts)[2] * 1e3:.2f} max {max(ts) * 1e3:.2f} "
-      f"leader_sum {int(r.leader.to(torch.int64).sum())} changes_sum {int(sum(r.changes))}")
+      f"leader_sum {int(r.leader.to(torch.int64).sum())} changes_sum {int(sum(r.changes))}{pairs}")
