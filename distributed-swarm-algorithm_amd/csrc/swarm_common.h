@@ -72,6 +72,7 @@ enum Slot {
     S_REORDER_DEG,    // reorder: the relabelled rows' degrees (n + 1 int32); the plan's moved-row counter
     S_REORDER_POS,    // reorder: the positions in input order (n x 2 f64)
     S_REORDER_ORDER,  // reorder: the cell order of the input positions (n int32)
+    S_CENSUS,         // task census: the verdict word, the holder cursor and one packed best-entry key per task
     S_NUM
 };
 

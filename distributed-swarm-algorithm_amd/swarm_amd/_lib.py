@@ -46,7 +46,8 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_board_destroy", "swarm_update_loop_board", "swarm_permute_rows", "swarm_graph_relabel",
            "swarm_resort_plan", "swarm_board_create_moving", "swarm_board_set_velocities", "swarm_board_positions",
            "swarm_board_refresh", "swarm_board_call_box", "swarm_update_loop_board_moving",
-           "swarm_graph_pairs_count", "swarm_graph_pairs_fill", "swarm_elect_pairs")
+           "swarm_graph_pairs_count", "swarm_graph_pairs_fill", "swarm_elect_pairs", "swarm_board_census",
+           "swarm_tasks_census")
 BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
 BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
 
@@ -85,6 +86,15 @@ class BoardState(ctypes.Structure):
     _fields_ = [("Ks", ctypes.c_int32), ("Kt", ctypes.c_int32)] + \
                [(k, ctypes.c_void_p) for k in ("caps", "status", "tab_task", "tab_winner", "tab_util", "claim_out",
                                                "conflict_out")]
+
+
+CENSUS_FIELDS = ("tentative", "locked", "assigned", "tables", "holder_lo", "holder_hi", "winner_lo", "winner_hi",
+                 "best_winner", "best_util")
+
+
+class Census(ctypes.Structure):
+    """swarm_census: the ten per-task arrays of a task census (device pointers)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in CENSUS_FIELDS]
 
 
 class Rows(ctypes.Structure):
@@ -264,6 +274,10 @@ def load(path: str = LIB_PATH):
         L.swarm_board_refresh.argtypes = [P, P, ctypes.POINTER(BoardDesc), P]
         L.swarm_board_call_box.argtypes = [P, P, d, i32, P, P]
         L.swarm_update_loop_board_moving.argtypes = L.swarm_update_loop_board.argtypes
+        L.swarm_board_census.argtypes = [P, i64, P, P, ctypes.POINTER(BoardState), P, ctypes.POINTER(Census), P, i64,
+                                         ctypes.POINTER(i64), P]
+        L.swarm_tasks_census.argtypes = [P, i64, P, i32, P, P, P, P, P, ctypes.POINTER(Census), P, i64,
+                                         ctypes.POINTER(i64), P]
         L.swarm_permute_rows.argtypes = [P, i64, P, i32, ctypes.POINTER(Rows), P]
         L.swarm_graph_relabel.argtypes = [P, i64, P, P, P, P, P, P]
         L.swarm_resort_plan.argtypes = [P, i64, P, P, d, P, P, ctypes.POINTER(i64), P]

@@ -1361,6 +1361,80 @@ class Swarm:
             a.task_claims = {int(task_ids[int(k)]): {"winner": int(w), "utility": float(u)}
                              for k, w, u in zip(tt[i], tw[i], tu[i]) if k >= 0 and w >= 0}
 
+    # ------------------------------------------------------------------ task census (U1-C)
+    def board_census(self, *, alive_only: bool = False, holders: bool = False) -> dict:
+        """What the swarm decided, per task of the board of set_task_board (contract U1-C; swarm_board_census):
+        a dict of ten device tensors of length T -- "tentative", "locked", "assigned", "tables" (int32 counts of
+        agents with that status of the task / with a claim-table entry for it), "holder_lo", "holder_hi" (the
+        lowest / highest agent ID among the ASSIGNED holders, -1 without one), "winner_lo", "winner_hi" (the
+        lowest / highest winner the table entries name; the tables agree iff they are equal; -1 without an
+        entry), "best_winner", "best_util" (the entry with the highest utility, ties to the lowest winner; -1 and
+        0.0 without one).  Bit-exact, whatever the storage order.  alive_only: only agents with fsm["alive"] are
+        counted.  holders: also "holders", every (task, agent ID) pair with status ASSIGNED as an (m, 2) int32
+        tensor sorted by (task, ID).  Nothing of the swarm is changed; rows set by hand that are not canonical
+        are refused (SwarmError ERR_ARG)."""
+        if not hasattr(self, "board"):
+            raise RuntimeError("no task board: call set_task_board() first")
+        b, mask = self.board, self._census_mask(alive_only)
+        if b["status"].shape[0] != self.n:
+            raise ValueError("the task board was set for another number of agents")
+        p = lambda t: _lib.ptr(t) if self.n else None  # noqa: E731
+        bs = _lib.BoardState(b["Ks"], b["Kt"], None, *[p(b[k]) for k in ("status", "tab_task", "tab_winner",
+                                                                        "tab_util")], None, None)
+
+        def call(ctx, ids, mask, out, pairs, cap, total):
+            return _lib.lib().swarm_board_census(ctx, self.n, ids, b["handle"], ctypes.byref(bs), mask, out, pairs,
+                                                 cap, total, _lib.stream())
+        return self._census(b["T"], call, mask, holders)
+
+    def task_census(self, *, alive_only: bool = False, holders: bool = False) -> dict:
+        """board_census for the 64-task board of set_tasks (swarm_tasks_census): the same dict."""
+        if not hasattr(self, "tasks"):
+            raise RuntimeError("no task board: call set_tasks() first")
+        b, mask = self.tasks, self._census_mask(alive_only)
+        if b["status_lo"].shape[0] != self.n:
+            raise ValueError("the task board was set for another number of agents")
+        p = lambda k: _lib.ptr(b[k]) if b[k].numel() else None  # noqa: E731
+
+        def call(ctx, ids, mask, out, pairs, cap, total):
+            return _lib.lib().swarm_tasks_census(ctx, self.n, ids, b["T"], p("status_lo"), p("status_hi"),
+                                                 p("tab_winner"), p("tab_util"), mask, out, pairs, cap, total,
+                                                 _lib.stream())
+        return self._census(b["T"], call, mask, holders)
+
+    def _census_mask(self, alive_only):
+        if not alive_only:
+            return None
+        if not hasattr(self, "fsm"):
+            raise RuntimeError("alive_only needs the protocol state: call protocol_reset() or run a loop first")
+        return self.fsm["alive"]
+
+    def _census(self, T, call, mask, holders) -> dict:
+        """The output tensors and the holder buffer of a census call: T + 1024 pairs at first, the call repeated
+        once with the exact count when the total came back larger."""
+        dev, n = self.device, self.n
+        res = {k: torch.empty(T, dtype=torch.float32 if k == "best_util" else torch.int32, device=dev)
+               for k in _lib.CENSUS_FIELDS}
+        pairs = torch.empty((0, 2), dtype=torch.int32, device=dev)
+        if T:  # (a board without tasks has nothing to count: ten empty tensors, no call)
+            out = _lib.Census(*[_lib.ptr(res[k]) for k in _lib.CENSUS_FIELDS])
+            total, cap = ctypes.c_int64(0), (T + 1024 if holders else 0)
+            with torch.cuda.device(dev):
+                for _ in range(2):
+                    buf = torch.empty((cap, 2), dtype=torch.int32, device=dev) if holders else None
+                    _lib.check(call(_lib.ctx(), _lib.ptr(self.ids) if n else None,
+                                    _lib.ptr(mask) if mask is not None and n else None, ctypes.byref(out),
+                                    _lib.ptr(buf), cap, ctypes.byref(total)))
+                    if not holders or total.value <= cap:
+                        break
+                    cap = total.value
+            if holders:
+                pairs = buf[:total.value]
+        if holders:
+            order = torch.argsort(pairs[:, 0].long() * (1 << 31) + pairs[:, 1].long())
+            res["holders"] = pairs[order].contiguous()
+        return res
+
     def _update_loop(self, ticks, sense_radius, obstacles, sensors, kill_ticks, dt, timeout, jitter, seed,
                      max_speed, mode, pull_frac, trace_every, radio_radius=None, tasks=None, channel=None,
                      board=None) -> dict:

@@ -1130,6 +1130,68 @@ int swarm_graph_relabel(swarm_ctx *ctx, int64_t n, const int32_t *from, const in
 int swarm_resort_plan(swarm_ctx *ctx, int64_t n, const double *pos, const int32_t *perm, double cell, int32_t *from,
                       int32_t *perm_out, int64_t *moved, void *stream);
 
+/*
+ * Task census (contract U1-C): the per-task outcome of a task board, reduced on the device.  No
+ * reference counterpart: the reference keeps every agent's tasks in its own dict.  Read-only: nothing of the board,
+ * the state or the agents is written.
+ *
+ * Agent i (storage index) is counted iff mask == NULL or mask[i] != 0 (mask: device, n bytes).  For every task k in
+ * [0, T), the ten arrays of swarm_census (device, T long each, all written by every successful call):
+ *   tentative / locked / assigned  (i32)  counted agents whose status of k is TENTATIVE / LOCKED / ASSIGNED;
+ *   tables                (i32)  counted agents whose claim table has an entry for k;
+ *   holder_lo / holder_hi (i32)  the lowest / highest agent ID (ids[i], not i) among the ASSIGNED holders; -1, -1
+ *                                when there is none;
+ *   winner_lo / winner_hi (i32)  the lowest / highest winner ID the counted table entries name (they agree iff the
+ *                                two are equal); -1, -1 without an entry;
+ *   best_winner / best_util (i32, f32)  the counted table entry with the highest utility, among equal utilities the
+ *                                lowest winner ID; -1, +0.0f without an entry.
+ * Utilities compare by the order-preserving integer image of their f32 bits (b < 0 ? ~b : b | 2^31), which defines
+ * the result for any bytes; the lows are minima of the IDs as unsigned words, the highs maxima as signed ones (the
+ * library's IDs are never negative, so both are the plain order).  Every output is a commutative integer
+ * reduction: the census is bit-exact, whatever the storage order and the kernel's schedule.
+ *
+ * holders (device, cap pairs of i32, 8-byte aligned; NULL with cap == 0): every (task, agent ID) pair with a
+ * counted ASSIGNED status, in any order, through a wave-aggregated cursor; never more than cap pairs are written.
+ * *n_holders (host, may be NULL) is the exact total, sum(assigned), which may exceed cap: the first
+ * min(cap, total) slots then hold true pairs, and a second call with cap >= total returns them all.
+ *
+ * swarm_board_census: the sparse board of swarm_update_loop_board (static or moving).  Of `state` only Ks, Kt,
+ * status, tab_task, tab_winner and tab_util are read.  swarm_tasks_census: the 64-task board of
+ * swarm_update_loop_tasks, from the two status words and the dense n x T tables; an entry is a tab_winner >= 0,
+ * status bits at or above T are no tasks and are ignored.  Both wait for the stream once, at the end.
+ *
+ * SWARM_ERR_ARG before the device is touched: a NULL ctx, board, state, out or array (ids and the state arrays may
+ * be NULL when n == 0); a board that is no live board of ctx; Ks or Kt outside [1, 4096]; T outside [0, 64] for the
+ * 64-task form; n outside [0, 2^31); cap < 0; holders NULL with cap > 0, or misaligned.
+ * SWARM_ERR_ARG from the device (swarm_board_census): rows that are not canonical, by the rule of
+ * swarm_update_loop_board's entry pass -- every status / tab_task entry -1 or a task in [0, T), every status code
+ * in 1..3, every row strictly ascending with the empties last.  The check is folded into the census pass: every
+ * entry is range-checked by the thread that loaded it before it indexes anything.  After this refusal the ten
+ * arrays and holders are unspecified; nothing outside them has been written.
+ * T == 0: success, nothing launched, *n_holders = 0.  n == 0: success, the arrays hold their empty values.
+ * Scratch: 8 T + 64 bytes of the ctx (a packed (utility image, ~winner) key per task).
+ */
+typedef struct {
+    int32_t *tentative;
+    int32_t *locked;
+    int32_t *assigned;
+    int32_t *tables;
+    int32_t *holder_lo;
+    int32_t *holder_hi;
+    int32_t *winner_lo;
+    int32_t *winner_hi;
+    int32_t *best_winner;
+    float *best_util;
+} swarm_census;
+
+int swarm_board_census(swarm_ctx *ctx, int64_t n, const int32_t *ids, const swarm_board *board,
+                       const swarm_board_state *state, const uint8_t *mask, const swarm_census *out, int32_t *holders,
+                       int64_t cap, int64_t *n_holders, void *stream);
+int swarm_tasks_census(swarm_ctx *ctx, int64_t n, const int32_t *ids, int32_t T, const uint64_t *status_lo,
+                       const uint64_t *status_hi, const int32_t *tab_winner, const float *tab_util,
+                       const uint8_t *mask, const swarm_census *out, int32_t *holders, int64_t cap,
+                       int64_t *n_holders, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
