@@ -28,6 +28,7 @@
 #include <random>
 #include <vector>
 
+#include "elect_schedule.h"  // next_round_batch
 #include "swarm_common.h"
 
 namespace swarm {
@@ -356,19 +357,6 @@ int comm_rank(const swarm_comm *comm, int *rank, int *nranks) {
 
 }  // namespace swarm
 
-// the frontier round launcher lives in elect.hip
-namespace swarm {
-int frontier_round_stepper(swarm_ctx *ctx, int t, const int32_t *rp, const int32_t *col, int32_t *L0,
-                           int32_t *L1, hipStream_t s);
-int frontier_ghosts_both(swarm_ctx *ctx, int t, const int32_t *rp, const int32_t *col, int64_t b_lo, int64_t n_lo,
-                         const int32_t *in_lo, int64_t b_hi, int64_t n_hi, const int32_t *in_hi, int32_t *L0,
-                         int32_t *L1, hipStream_t s);
-int frontier_round_totals(swarm_ctx *ctx, int t0, int t1, unsigned long long *dtot, hipStream_t s);
-int frontier_check_compact(swarm_ctx *ctx, const int32_t *rp, const int32_t *col, hipStream_t s);
-int64_t frontier_il_min(int64_t n);
-bool frontier_round_dense(int t);
-}  // namespace swarm
-
 extern "C" {
 
 int swarm_comm_available(void) { return swarm::rccl().ok ? 1 : 0; }
@@ -667,7 +655,7 @@ int swarm_elect_sharded_ex(swarm_ctx *ctx, swarm_comm *comm, const swarm_shard *
             }
         }
         t = tend + 1;
-        batch = next_round_batch(hist.data(), hist.size(), batch, kMaxBatch);
+        batch = next_round_batch(hist.data(), hist.size(), batch, kMaxBatch, batch_doubling_only());
     }
     *rounds_exec = found > 0 ? found : max_rounds;
     return found > 0 ? SWARM_OK : SWARM_NOT_CONVERGED;

@@ -67,6 +67,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "elect_schedule.h"
 #include "swarm_common.h"
 
 namespace swarm {
@@ -1645,47 +1646,59 @@ size_t act_bytes(int64_t n_all) {  // one parity: every chunk of the stamp layou
     return size_t(m.M) << m.cshift;
 }
 
+// One dense launch's arguments; go<> picks the kernel, marked() its MARK from act_w.
+template <typename Off>
+struct DenseLaunch {
+    unsigned grid;
+    hipStream_t s;
+    const Off *rp;
+    const int32_t *lin;
+    int32_t *lout;
+    int64_t n, c_lo, n_count;
+    unsigned long long *ring, *tot;
+    uint8_t *act_w;
+    StampMap sm;
+    int t, guard;
+    const Off *hrp;  // DIR only
+    const int32_t *hcol;
+    template <bool MARK, bool DIR, bool FLAT, typename CT>
+    void go(CT cols) const {
+        hipLaunchKernelGGL((k_elect_dense<Off, MARK, DIR, FLAT, CT>), dim3(grid), dim3(kBlock), 0, s, rp, cols, lin,
+                           lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, DIR ? hrp : nullptr,
+                           DIR ? hcol : nullptr);
+    }
+    template <bool FLAT, typename CT>
+    void marked(CT cols) const {
+        if (act_w)
+            go<true, false, FLAT>(cols);
+        else
+            go<false, false, FLAT>(cols);
+    }
+};
+
 template <typename Off>
 int launch_dense_round(const Off *rp, const int32_t *col, const int32_t *lin, int32_t *lout, int64_t n, int64_t c_lo,
                        int64_t n_count,
                        unsigned long long *ring, unsigned long long *tot, uint8_t *act_w, StampMap sm, int t,
                        int guard, hipStream_t s, const Off *hrp = nullptr, const int32_t *hcol = nullptr,
                        const int16_t *c16 = nullptr) {
-    const unsigned grid = grid_for((n + 63) / 64, kWavesPerBlock, unsigned(tuning().dense_blocks));
+    const DenseLaunch<Off> d{grid_for((n + 63) / 64, kWavesPerBlock, unsigned(tuning().dense_blocks)),
+                            s, rp, lin, lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, hrp, hcol};
     const Col32 c32{col};
-    if (!hrp && sizeof(Off) == 4 && tuning().dense_flat && c16) {
-        const Col16 cc{c16};
+    const bool flat = !hrp && sizeof(Off) == 4 && tuning().dense_flat;
+    if (flat && c16) {
         Col16A ca;
         ca.p = c16;
-        const bool vec = tuning().dense_vec && (reinterpret_cast<uintptr_t>(c16) & 15) == 0;
-        if (act_w && vec)
-            hipLaunchKernelGGL((k_elect_dense<Off, true, false, true, Col16A>), dim3(grid), dim3(kBlock), 0, s, rp, ca,
-                               lin, lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, nullptr, nullptr);
-        else if (vec)
-            hipLaunchKernelGGL((k_elect_dense<Off, false, false, true, Col16A>), dim3(grid), dim3(kBlock), 0, s, rp, ca,
-                               lin, lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, nullptr, nullptr);
-        else if (act_w)
-            hipLaunchKernelGGL((k_elect_dense<Off, true, false, true, Col16>), dim3(grid), dim3(kBlock), 0, s, rp, cc,
-                               lin, lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, nullptr, nullptr);
+        if (tuning().dense_vec && (reinterpret_cast<uintptr_t>(c16) & 15) == 0)
+            d.template marked<true>(ca);
         else
-            hipLaunchKernelGGL((k_elect_dense<Off, false, false, true, Col16>), dim3(grid), dim3(kBlock), 0, s, rp, cc,
-                               lin, lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, nullptr, nullptr);
-    } else if (!hrp && sizeof(Off) == 4 && tuning().dense_flat) {
-        if (act_w)
-            hipLaunchKernelGGL((k_elect_dense<Off, true, false, true>), dim3(grid), dim3(kBlock), 0, s, rp, c32, lin,
-                               lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, nullptr, nullptr);
-        else
-            hipLaunchKernelGGL((k_elect_dense<Off, false, false, true>), dim3(grid), dim3(kBlock), 0, s, rp, c32, lin,
-                               lout, n, c_lo, n_count, ring, tot, act_w, sm, t, guard, nullptr, nullptr);
-    } else if (act_w && hrp)
-        hipLaunchKernelGGL((k_elect_dense<Off, true, true>), dim3(grid), dim3(kBlock), 0, s, rp, c32, lin, lout, n,
-                           c_lo, n_count, ring, tot, act_w, sm, t, guard, hrp, hcol);
-    else if (act_w)
-        hipLaunchKernelGGL((k_elect_dense<Off, true>), dim3(grid), dim3(kBlock), 0, s, rp, c32, lin, lout, n, c_lo, n_count, ring,
-                           tot, act_w, sm, t, guard, nullptr, nullptr);
+            d.template marked<true>(Col16{c16});
+    } else if (flat)
+        d.template marked<true>(c32);
+    else if (act_w && hrp)
+        d.template go<true, true, false>(c32);
     else
-        hipLaunchKernelGGL((k_elect_dense<Off, false>), dim3(grid), dim3(kBlock), 0, s, rp, c32, lin, lout, n, c_lo, n_count, ring,
-                           tot, act_w, sm, t, guard, nullptr, nullptr);
+        d.template marked<false>(c32);
     SW_LAUNCHED();
     return SWARM_OK;
 }
@@ -1740,22 +1753,13 @@ int frontier_alloc(swarm_ctx *ctx, int64_t n_rows, int64_t n_all, int32_t *L0, i
     return SWARM_OK;
 }
 
-enum RoundKind { RK_DENSE = 0, RK_DENSE_MARK = 1, RK_SPARSE = 2 };
+// Kind of frontier round t under the process's SWARM_DENSE_ROUNDS (elect_schedule.h has the rule).
+RoundKind plan_round(int t) { return swarm::plan_round(t, tuning().dense_rounds); }
 
-// Kind of frontier round t: the first dense_rounds rounds dense (nearly every agent changes;
-// measured best at 9 for 10M agents with the 16-bit columns: 24.15 vs 24.23 ms at 8), the last of
-// them marking, then sparse.
-RoundKind plan_round(int t) {
-    const int R = tuning().dense_rounds;
-    if (t < R) return RK_DENSE;
-    if (t == R) return RK_DENSE_MARK;
-    return RK_SPARSE;
-}
-
-// A launch of an election that runs pair rounds (elect_impl).  Once a launch has covered two rounds the launch
-// counter lc lags the round: the leader buffers, the stamp parity, the stamp value and the stamp clears follow
-// lc, the counter ring follows the round t.  NULL: lc = t, guard_round = t - 2, form PF_SINGLE.
-enum PairForm { PF_SINGLE = 0, PF_MARK = 1, PF_PAIR = 2 };
+// A launch of an election that runs pair rounds (elect_schedule.h, LaunchPlan, with the two-hop index).  Once a
+// launch has covered two rounds the launch counter lc lags the round: the leader buffers, the stamp parity, the
+// stamp value and the stamp clears follow lc, the counter ring follows the round t.  NULL: lc = t, guard_round
+// = t - 2, form PF_SINGLE.
 struct RoundPlan {
     int lc;              // this launch's number (1-based)
     int guard_round;     // the last round of launch lc - 2, whose total the launch before this one published
@@ -1812,18 +1816,26 @@ void launch_sparse(const Off *rp, CT cols, const Frontier &f, int t, int guard, 
         launch_sparse_lf<Off, S, DIR, CT, PRUNE, unsigned(SWARM_LIST_EXTRA)>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
 }
 
+// ... with the chunk size of the frontier's stamp layout: 512-stamp chunks for a small swarm (4x the workgroups)
+template <typename Off, bool DIR, typename CT, bool PRUNE>
+void launch_sparse_sized(const Off *rp, CT cols, const Frontier &f, int t, int guard, unsigned flags, const Off *hrp,
+                         const int32_t *hcol, hipStream_t s, const RoundPlan *pl = nullptr) {
+    if (f.sm.cshift == 9)
+        launch_sparse<Off, 2, DIR, CT, PRUNE>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
+    else
+        launch_sparse<Off, kScan, DIR, CT, PRUNE>(rp, cols, f, t, guard, flags, hrp, hcol, s, pl);
+}
+
 // The sparse round of a symmetric graph: chunk size and column type from the frontier, PRUNE from
 // SWARM_MARK_PRUNE.
 template <typename Off, bool PRUNE>
 int launch_sparse_round(const Off *rp, const int32_t *col, const Frontier &f, int t, int guard, unsigned flags,
                         hipStream_t s, const RoundPlan *pl = nullptr) {
-    const bool small = f.sm.cshift == 9;  // small swarm: 512-agent chunks, 4x the workgroups
-    const Col32 c32{col};
     if (pl && pl->form != PF_SINGLE) {
         if constexpr (sizeof(Off) == 4) {
             SW_ARG(f.c16 && !f.c16_esc && pl->rp2 && pl->c2 && tuning().list_mask == kListDefault,
                    "pair rounds need the unescaped 16-bit columns, the two-hop index and the default list levers");
-            if (small)
+            if (f.sm.cshift == 9)
                 launch_sparse_pairform<2>(rp, Col16{f.c16}, f, t, guard, flags, s, *pl);
             else
                 launch_sparse_pairform<kScan>(rp, Col16{f.c16}, f, t, guard, flags, s, *pl);
@@ -1833,26 +1845,15 @@ int launch_sparse_round(const Off *rp, const int32_t *col, const Frontier &f, in
             SW_ARG(false, "pair rounds: int32 row offsets only");
         }
     }
-    if (f.c16 && f.c16_esc && small)
-        launch_sparse<Off, 2, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s, pl);
-    else if (f.c16 && f.c16_esc)
-        launch_sparse<Off, kScan, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s, pl);
-    else if (f.c16 && small)
-        launch_sparse<Off, 2, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s, pl);
+    if (f.c16 && f.c16_esc)
+        launch_sparse_sized<Off, false, Col16E, PRUNE>(rp, Col16E{f.c16, col}, f, t, guard, flags, nullptr, nullptr, s, pl);
     else if (f.c16)
-        launch_sparse<Off, kScan, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s, pl);
-    else if (small)
-        launch_sparse<Off, 2, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s, pl);
+        launch_sparse_sized<Off, false, Col16, PRUNE>(rp, Col16{f.c16}, f, t, guard, flags, nullptr, nullptr, s, pl);
     else
-        launch_sparse<Off, kScan, false, Col32, PRUNE>(rp, c32, f, t, guard, flags, nullptr, nullptr, s, pl);
+        launch_sparse_sized<Off, false, Col32, PRUNE>(rp, Col32{col}, f, t, guard, flags, nullptr, nullptr, s, pl);
     SW_LAUNCHED();
     return SWARM_OK;
 }
-
-// Whether sparse round t clears the buffer it marks into first (parity t+1, last read by round t-1):
-// every 256 rounds, per parity, so no stamp outlives the 510 rounds after which its value recurs
-// (take_stamps).
-bool clear_due(int t) { return t > 2 && ((t - 1) & 255) < 2; }
 
 // hrp/hcol: the transpose CSR of a directed graph (who hears each agent), or NULL (symmetric).
 // cleared_for (optional, kept by the caller across the rounds of one run): the round whose clear the
@@ -1881,10 +1882,7 @@ int launch_frontier_round(const Off *rp, const int32_t *col, const Frontier &f, 
         *cleared_for = lc + 1;
     }
     if (hrp) {  // directed: the marks go to hearers, whose leaders the riser did not read -- never pruned
-        if (f.sm.cshift == 9)
-            launch_sparse<Off, 2, true, Col32, false>(rp, Col32{col}, f, t, guard, flags, hrp, hcol, s);
-        else
-            launch_sparse<Off, kScan, true, Col32, false>(rp, Col32{col}, f, t, guard, flags, hrp, hcol, s);
+        launch_sparse_sized<Off, true, Col32, false>(rp, Col32{col}, f, t, guard, flags, hrp, hcol, s);
         SW_LAUNCHED();
         return SWARM_OK;
     }
@@ -1954,6 +1952,421 @@ int col16_verdict(unsigned hflag, const char *who) {
     return SWARM_OK;
 }
 
+// ------------------------------------------------------------------ swarm_elect*: the host loop
+// elect_impl below reads top to bottom as these stages; what they decide -- the rounds of a launch, its leader
+// buffers and guard, how far a batch runs ahead of the read-back, the buffer of the final state -- is
+// elect_schedule.h's ElectSchedule, which tests/elect_schedule/ drives on the CPU.  The stages only enqueue
+// what the schedule plans, in its order.
+constexpr int kMaxBatch = 256;  // rounds per read-back (a batch with its look-ahead stays below kRing / 2)
+
+// The graph an election was given, with its edge count once check_graph has read (or recalled) it.
+template <typename Off>
+struct ElectGraph {
+    int64_t n;
+    const Off *rp;
+    const int32_t *col;
+    const Off *hrp;  // the transpose CSR of a directed graph (who hears each agent), or NULL (symmetric)
+    const int32_t *hcol;
+    const int16_t *c16;
+    const int32_t *rp2;  // the two-hop index (swarm_elect_pairs), or NULL
+    const int16_t *c2;
+    Off e_total;
+};
+
+// Stage: the graph's validation.  16-bit columns are checked before any round reads them (one pass over the
+// columns, read back with the edge count): escaped columns or a foreign buffer are refused, never gathered
+// through.
+template <typename Off>
+int check_graph(swarm_ctx *ctx, ElectGraph<Off> &g, bool trust_c16, hipStream_t s) {
+    SW_ARG(!g.c16 || !esc_registered(ctx, g.c16), "col16 holds swarm_graph_compact_escaped's columns (escapes)");
+    // SWARM_ELECT_TRUST_C16 with this ctx's record of the buffer: its columns and the edge count are known
+    const swarm_ctx::C16Built *rec =
+        (trust_c16 && g.c16 && !g.hrp) ? c16_record(ctx, g.c16, g.rp, g.col, g.n) : nullptr;
+    g.e_total = 0;
+    if (rec) {
+        g.e_total = Off(rec->e_total);
+    } else {
+        unsigned c16_bad = 0;
+        if (g.c16) {
+            if (int rc = enqueue_col16_check<Off>(ctx, g.rp, g.c16, g.col, false, g.n, g.n, &c16_bad, s)) return rc;
+        }
+        SW_HIP(hipMemcpyAsync(&g.e_total, g.rp + g.n, sizeof(Off), hipMemcpyDeviceToHost, s));
+        SW_HIP(hipStreamSynchronize(s));
+        if (int rc = col16_verdict(c16_bad, "swarm_elect_compact")) return rc;
+    }
+    SW_ARG(g.e_total == 0 || g.col != nullptr, "col is NULL but the graph has edges");
+    // the int32-CSR kernels address with 32-bit byte offsets (gather_listed's ld4 / Col16::at32):
+    // 4-byte columns need < 2^30 edges, 2-byte ones < 2^31 (less a margin for the clamped offsets a
+    // window or a pass computes past its row's end) -- C5's 100M agents (1.6e9 edges) fit with them
+    const bool c16_only = g.c16 && !g.hrp && tuning().dense_flat;
+    const int64_t e_cap = c16_only ? (int64_t(1) << 31) - (int64_t(1) << 20) : (int64_t(1) << 30);
+    SW_ARG(sizeof(Off) == 8 || (g.n < (int64_t(1) << 30) && int64_t(g.e_total) < e_cap),
+           "int32 CSR supports < 2^30 agents and edges (< 2^31 - 2^20 edges with 16-bit columns): use "
+           "swarm_elect_i64 / swarm_elect_compact_i64");
+    if (g.hrp) {  // directed: the transpose must hold the same edges
+        Off h_total = 0;
+        SW_HIP(hipMemcpyAsync(&h_total, g.hrp + g.n, sizeof(Off), hipMemcpyDeviceToHost, s));
+        SW_HIP(hipStreamSynchronize(s));
+        SW_ARG(h_total == g.e_total, "hear_row_ptr[n] != row_ptr[n]: not the transpose of the graph");
+        SW_ARG(h_total == 0 || g.hcol != nullptr, "hear_col is NULL but the graph has edges");
+    }
+    return SWARM_OK;
+}
+
+// Stage: the leader buffers, the counter ring and (FRONTIER) the stamps.
+struct ElectBuffers {
+    const int32_t *ids;
+    int32_t *bufs[2];  // bufs[0] = leader
+    bool frontier;     // FRONTIER mode: f holds the stamps and the ring
+    bool skip_copy;
+    Frontier f;
+    unsigned long long *ring;
+    StampMap il_map, ag_map;  // the stamp layouts: interleaved, agent order
+};
+
+int setup_buffers(swarm_ctx *ctx, int64_t n, const int32_t *ids, int32_t *leader, const int16_t *c16, bool frontier,
+                  hipStream_t s, ElectBuffers *b) {
+    b->ids = ids;
+    b->frontier = frontier;
+    b->bufs[0] = leader;
+    SW_ALLOC(b->bufs[1], ctx, S_LEADER_B, size_t(n) * 4);
+    // The leader buffers start as copies of ids -- unless rounds 1 and 2 are both dense: round 1 then reads
+    // ids itself and writes every entry of bufs[1], round 2 every entry of bufs[0] = leader, and no later
+    // round reads anything older.  A call whose ids overlaps leader keeps the copies.
+    const bool aliased = ids < leader + n && leader < ids + n;
+    b->skip_copy = tuning().skip_init_copy && !aliased && (!frontier || tuning().dense_rounds >= 2);
+    if (!b->skip_copy) SW_HIP(hipMemcpyAsync(leader, ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
+    b->f = Frontier{};
+    if (frontier) {
+        if (!b->skip_copy) SW_HIP(hipMemcpyAsync(b->bufs[1], ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
+        if (int rc = frontier_alloc(ctx, n, n, b->bufs[0], b->bufs[1], &b->f, s)) return rc;
+        b->ring = b->f.ring;
+        b->f.c16 = c16;
+    } else {
+        SW_ALLOC(b->ring, ctx, S_CHANGES, ring_bytes());
+        SW_HIP(hipMemsetAsync(b->ring, 0, ring_bytes(), s));
+        ctx->step_rows = ctx->step_all = 0;  // the stepper state is gone
+    }
+    b->il_map = stamp_map(n, true);
+    b->ag_map = stamp_map(n, false);
+    return SWARM_OK;
+}
+
+// Stage: the read-back channel.  The per-round totals land in mapped host memory, written by k_batch_totals
+// itself, then the batch's epoch word after them (k_signal), which the host spins on.
+struct ReadBack {
+    // a tag no counter value reaches, then the batch number (the word is shared with other calls)
+    static constexpr unsigned long long kTag = 0xE1EC7ull << 40;
+    unsigned long long *ring = nullptr, *hbuf = nullptr, *dtot = nullptr, *h_epoch = nullptr, *d_epoch = nullptr;
+    unsigned long long ep = 0;
+    hipStream_t s = nullptr;
+
+    int open(swarm_ctx *ctx, unsigned long long *ring_, hipStream_t s_) {
+        void *dmap = nullptr;
+        hbuf = static_cast<unsigned long long *>(mapped(ctx, size_t(kCounters) * 8 * kMaxBatch + 128, &dmap));
+        if (!hbuf) return SWARM_ERR_OOM;
+        ring = ring_;
+        s = s_;
+        dtot = static_cast<unsigned long long *>(dmap);
+        h_epoch = hbuf + size_t(kCounters) * kMaxBatch;
+        d_epoch = dtot + size_t(kCounters) * kMaxBatch;
+        __atomic_store_n(h_epoch, 0ull, __ATOMIC_RELEASE);
+        return SWARM_OK;
+    }
+    // per-round totals of rounds (from, upto], reduced on device into mapped host memory, then the
+    // batch's epoch word: one launch (SWARM_FUSED_READBACK) or two
+    int enqueue(int from, int upto) {
+        if (tuning().fused_readback) {
+            hipLaunchKernelGGL(k_batch_totals_signal, dim3(1), dim3(kReadbackThreads), 0, s, ring, from + 1,
+                               upto - from, dtot, d_epoch, kTag | ++ep);
+            SW_LAUNCHED();
+            return SWARM_OK;
+        }
+        hipLaunchKernelGGL(k_batch_totals, dim3(upto - from), dim3(kWave), 0, s, ring, from + 1, dtot);
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, s, d_epoch, kTag | ++ep);
+        SW_LAUNCHED();
+        return SWARM_OK;
+    }
+    int wait() const { return wait_mapped_word(h_epoch, kTag | ep, s, "election read-back"); }
+};
+
+// What an election accumulates over the rounds it has read (swarm_elect_stats).
+struct ElectTotals {
+    int64_t act_sum = 0, edge_sum = 0, chg_sum = 0, dense_rounds = 0;
+    double bytes = 0.0, sp_bytes = 0.0;
+    double k_ms = 0.0, sp_ms = 0.0;  // the timer's
+    int64_t timed_rounds = 0, sp_launches = 0;
+};
+
+// Stage: the optional per-round timer (SWARM_ELECT_TIMED).  Dense rounds (and every round when a per-round log
+// is written) get an event pair each; a batch's run of back-to-back sparse rounds gets ONE pair around it --
+// events between every launch would add their own cost to each round (rocprof's per-dispatch durations are
+// the reference for this figure).  Timed runs have no look-ahead: a batch's rounds are exactly the rounds read.
+struct RoundTimer {
+    bool on = false, per_round = false;  // per_round: the round log wants every round's own time
+    std::vector<hipEvent_t> ev;
+    std::vector<RoundKind> kinds = std::vector<RoundKind>(kMaxBatch);
+    std::vector<float> ktime = std::vector<float>(kMaxBatch);
+    int t0 = 1;     // the batch's first round
+    int seg_n = 0;  // sparse launches inside this batch's segment
+    ~RoundTimer() {
+        for (auto x : ev) (void)hipEventDestroy(x);
+    }
+    int open(bool timed, bool logged) {
+        on = timed;
+        per_round = logged;
+        if (on) {
+            ev.resize(2 * kMaxBatch + 2);
+            for (auto &x : ev) SW_HIP(hipEventCreate(&x));
+        }
+        return SWARM_OK;
+    }
+    void begin_batch(int t) {
+        t0 = t;
+        seg_n = 0;
+    }
+    bool in_segment(const LaunchPlan &l) const { return on && l.kind == RK_SPARSE && !per_round; }
+    int before(const LaunchPlan &l, hipStream_t s) {
+        for (int i = 0; i < l.rounds && l.t + i - t0 < kMaxBatch; ++i) kinds[l.t + i - t0] = l.kind;
+        if (in_segment(l) && seg_n++ == 0) SW_HIP(hipEventRecord(ev[2 * kMaxBatch], s));
+        if (on && !in_segment(l)) SW_HIP(hipEventRecord(ev[2 * (l.t - t0)], s));
+        return SWARM_OK;
+    }
+    int after(const LaunchPlan &l, hipStream_t s) {
+        if (on && !in_segment(l)) SW_HIP(hipEventRecord(ev[2 * (l.t - t0) + 1], s));
+        return SWARM_OK;
+    }
+    int end_launches(hipStream_t s) {
+        if (seg_n) SW_HIP(hipEventRecord(ev[2 * kMaxBatch + 1], s));
+        return SWARM_OK;
+    }
+    // every launched round's kernel time (rocprof's view) of rounds t0..tend
+    int collect(int tend, ElectTotals &tot, hipStream_t s) {
+        if (!on) return SWARM_OK;
+        SW_HIP(hipStreamSynchronize(s));
+        for (int r = t0; r <= tend; ++r) {
+            if (seg_n && kinds[r - t0] == RK_SPARSE) continue;  // in the segment (a pair: both its rounds)
+            float x = 0;
+            SW_HIP(hipEventElapsedTime(&x, ev[2 * (r - t0)], ev[2 * (r - t0) + 1]));
+            tot.k_ms += x;
+            ++tot.timed_rounds;
+            if (kinds[r - t0] == RK_SPARSE) {
+                tot.sp_ms += x;
+                ++tot.sp_launches;
+            }
+            ktime[r - t0] = x;
+        }
+        if (seg_n) {
+            float x = 0;
+            SW_HIP(hipEventElapsedTime(&x, ev[2 * kMaxBatch], ev[2 * kMaxBatch + 1]));
+            tot.k_ms += x;
+            tot.sp_ms += x;
+            tot.timed_rounds += seg_n;
+            tot.sp_launches += seg_n;
+        }
+        return SWARM_OK;
+    }
+};
+
+// One election call: its graph, buffers, channel, timer and schedule.
+template <typename Off>
+struct ElectRun {
+    swarm_ctx *ctx;
+    ElectGraph<Off> g;
+    hipStream_t s;
+    int64_t *changes_host;
+    ElectBuffers b;
+    ReadBack rb;
+    RoundTimer tm;
+    ElectTotals tot;
+    FILE *rlog = nullptr;  // SWARM_ROUND_LOG=path: one line per round (tuning aid)
+    int cleared_for = 0;   // the launch whose stamp clear the launch before it did in its own launch
+    ~ElectRun() {
+        if (rlog) fclose(rlog);
+    }
+};
+
+// The per-round counters of rounds (read_upto, upto], read back into hbuf: the schedule's history, the stats.
+template <typename Off>
+void consume(ElectRun<Off> &run, ElectSchedule &sc, int upto) {
+    const int r0 = sc.read_upto() + 1;
+    const int taken = sc.take_counts(run.rb.hbuf + C_CHG, kCounters, upto);
+    const int64_t n = run.g.n, e = int64_t(run.g.e_total);
+    ElectTotals &tot = run.tot;
+    for (int r = r0; r < r0 + taken; ++r) {
+        const unsigned long long *rb = run.rb.hbuf + size_t(r - r0) * kCounters;
+        const int64_t c = int64_t(rb[C_CHG]);
+        const RoundKind kind = sc.kind_of(r);
+        const bool dn = kind != RK_SPARSE;
+        if (run.changes_host) run.changes_host[r - 1] = c;
+        const int64_t act = dn ? n : int64_t(rb[C_ACT]);
+        const int64_t ed = dn ? e : int64_t(rb[C_EDGE]);
+        tot.act_sum += act;
+        tot.edge_sum += ed;
+        tot.chg_sum += c;
+        tot.dense_rounds += dn ? 1 : 0;
+        const double rbytes = round_bytes(dn, n, e, act, ed);
+        tot.bytes += rbytes;
+        if (kind == RK_SPARSE) tot.sp_bytes += rbytes;
+        if (run.rlog)
+            fprintf(run.rlog, "%d %lld %lld %lld %d %.2f\n", r, (long long)c, (long long)act, (long long)ed,
+                    int(kind), run.tm.on && r >= run.tm.t0 ? run.tm.ktime[r - run.tm.t0] * 1e3 : 0.0);
+    }
+}
+
+// The counters of rounds (read_upto, upto] read back and consumed (every launched round drained).
+template <typename Off>
+int read_rounds(ElectRun<Off> &run, ElectSchedule &sc, int upto) {
+    if (upto <= sc.read_upto()) return SWARM_OK;
+    if (int rc = run.rb.enqueue(sc.read_upto(), upto)) return rc;
+    if (int rc = run.rb.wait()) return rc;
+    consume(run, sc, upto);
+    return SWARM_OK;
+}
+
+// Stage: one launch of the schedule.
+template <typename Off>
+int launch_planned(ElectRun<Off> &run, const LaunchPlan &l, bool pair_ok) {
+    const ElectGraph<Off> &g = run.g;
+    ElectBuffers &b = run.b;
+    if (!b.frontier)  // DENSE mode
+        return launch_dense_round<Off>(g.rp, g.col, (l.t == 1 && b.skip_copy) ? b.ids : b.bufs[(l.t - 1) & 1],
+                                       b.bufs[l.t & 1], g.n, 0, g.n, b.ring, nullptr, nullptr, StampMap{}, l.t, 1,
+                                       run.s, nullptr, nullptr, g.c16);
+    if (l.t == 1 && b.skip_copy) {  // a dense round (dense_rounds >= 2) that reads ids
+        Frontier f1 = b.f;
+        f1.L[0] = const_cast<int32_t *>(b.ids);
+        f1.sm = f1.wsm = b.il_map;
+        return launch_frontier_round<Off>(g.rp, g.col, f1, l.t, l.kind, 1, run.s, g.hrp, g.hcol);
+    }
+    // marks for the next launch: interleaved layout while rounds are busy (balance), agent order once they
+    // are sparse (locality of the few gathers)
+    b.f.sm = l.rd_il ? b.il_map : b.ag_map;
+    b.f.wsm = l.wr_il ? b.il_map : b.ag_map;
+    const RoundPlan pl{l.lc, l.guard_round, l.form, tuning().pair_lanes, g.rp2, g.c2};
+    return launch_frontier_round<Off>(g.rp, g.col, b.f, l.t, l.kind, 1, run.s, g.hrp, g.hcol, &run.cleared_for,
+                                      pair_ok ? &pl : nullptr);
+}
+
+// Stage: one batch -- its launches with the read-back enqueued where the schedule puts it, the wait, the counts.
+template <typename Off>
+int run_batch(ElectRun<Off> &run, ElectSchedule &sc) {
+    const BatchPlan bp = sc.begin_batch();
+    const int from = sc.read_upto();
+    if (bp.read_first) {
+        if (int rc = run.rb.enqueue(from, bp.tread)) return rc;
+    }
+    run.tm.begin_batch(bp.t);
+    LaunchPlan l;
+    while (sc.next_launch(&l)) {
+        if (int rc = run.tm.before(l, run.s)) return rc;
+        if (int rc = launch_planned(run, l, sc.params().pair_ok)) return rc;
+        if (int rc = run.tm.after(l, run.s)) return rc;
+        if (l.totals_behind) {
+            if (int rc = run.rb.enqueue(from, bp.tread)) return rc;
+        }
+    }
+    if (int rc = run.tm.end_launches(run.s)) return rc;
+    if (int rc = run.rb.wait()) return rc;
+    if (int rc = run.tm.collect(bp.tend, run.tot, run.s)) return rc;
+    consume(run, sc, bp.tread);
+    sc.size_next_batch();
+    return SWARM_OK;
+}
+
+// Stage: the one-workgroup tail (opt-in experiment) from round launched + 1: drain, collect the marked agents,
+// run k_tail_wg, read its rounds' counters.  The schedule adopts the rounds it ran; the frontier rounds go on
+// from there.
+template <typename Off>
+int tail_rounds(ElectRun<Off> &run, ElectSchedule &sc, int cap) {
+    if (int rc = read_rounds(run, sc, sc.launched())) return rc;
+    if (!sc.tail_start_ok()) return SWARM_OK;
+    hipStream_t s = run.s;
+    Frontier &f = run.b.f;
+    const int t0 = sc.launched() + 1;
+    const int t_end = std::min(sc.params().max_rounds, t0 + 199);  // <= 200 rounds: one counter read-back
+    char *tb;
+    const size_t clk_words = tuning().tail_log ? 2 * 201 : 0;
+    SW_ALLOC(tb, run.ctx, S_LIST, 64 + size_t(kTailCap) * 4 + clk_words * 8);
+    unsigned *gcount = reinterpret_cast<unsigned *>(tb);
+    int32_t *glist = reinterpret_cast<int32_t *>(tb + 64);
+    unsigned long long *clk = clk_words ? reinterpret_cast<unsigned long long *>(tb + 64 + size_t(kTailCap) * 4)
+                                        : nullptr;
+    SW_HIP(hipMemsetAsync(gcount, 0, 4, s));
+    f.sm = sc.reads_interleaved() ? run.b.il_map : run.b.ag_map;
+    const dim3 cgrid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
+    if (f.sm.cshift == 9)  // small swarm: 512-stamp chunks (2 per thread)
+        hipLaunchKernelGGL((k_tail_collect<2>), cgrid, dim3(kBlock), 0, s, f, t0, glist, gcount, cap);
+    else
+        hipLaunchKernelGGL((k_tail_collect<kScan>), cgrid, dim3(kBlock), 0, s, f, t0, glist, gcount, cap);
+    SW_LAUNCHED();
+    const int64_t n16 = int64_t(2 * act_bytes(run.g.n)) / 16;
+    hipLaunchKernelGGL(k_tail_clear, dim3(grid_for(n16, kBlock, 2048)), dim3(kBlock), 0, s,
+                       reinterpret_cast<uint4 *>(f.act[0]), n16, gcount, cap);
+    SW_LAUNCHED();
+    f.wsm = run.b.ag_map;  // hand-back marks in agent order
+    // out[0..3] in mapped memory after the batch totals' epoch word
+    unsigned long long *h_out = run.rb.h_epoch + 1, *d_out = run.rb.d_epoch + 1;
+    const unsigned long long tep = (0x7A11ull << 40) | ++run.rb.ep;
+    __atomic_store_n(&h_out[3], 0ull, __ATOMIC_RELEASE);
+    const int32_t *rp32 = reinterpret_cast<const int32_t *>(run.g.rp);
+    if (run.g.c16)
+        hipLaunchKernelGGL((k_tail_wg<Col16>), dim3(1), dim3(kTailThreads), 0, s, rp32, Col16{run.g.c16}, f, glist,
+                           gcount, t0, t_end, cap, d_out, tep, clk);
+    else
+        hipLaunchKernelGGL((k_tail_wg<Col32>), dim3(1), dim3(kTailThreads), 0, s, rp32, Col32{run.g.col}, f, glist,
+                           gcount, t0, t_end, cap, d_out, tep, clk);
+    SW_LAUNCHED();
+    if (int rc = wait_mapped_word(&h_out[3], tep, s, "one-workgroup tail")) return rc;
+    const unsigned long long why = __atomic_load_n(&h_out[1], __ATOMIC_ACQUIRE);
+    const int last = int(__atomic_load_n(&h_out[0], __ATOMIC_ACQUIRE));
+    if (why == TAIL_NOT_STARTED) {
+        sc.tail_not_started();
+        return SWARM_OK;
+    }
+    if (clk) {  // experiment aid: per-round microseconds (100 MHz wall clock) and marked agents
+        SW_HIP(hipStreamSynchronize(s));
+        std::vector<unsigned long long> hc(clk_words);
+        SW_HIP(hipMemcpy(hc.data(), clk, clk_words * 8, hipMemcpyDeviceToHost));
+        for (int r = t0; r < last; ++r)
+            fprintf(stderr, "[tail] round %d marked %llu us %.2f\n", r, hc[2 * (r - t0) + 1],
+                    double(hc[2 * (r - t0 + 1)] - hc[2 * (r - t0)]) / 100.0);
+    }
+    sc.adopt_tail(last);
+    return read_rounds(run, sc, last);
+}
+
+// Stage: the end of the run -- the final state into leader (ElectSchedule::end has the rule), the FSM states,
+// the statistics.
+template <typename Off>
+int finish(ElectRun<Off> &run, const ElectSchedule &sc, uint8_t *state, int32_t *rounds_exec, swarm_elect_stats *st) {
+    const ScheduleEnd e = sc.end();
+    const int64_t n = run.g.n;
+    int32_t *leader = run.b.bufs[0];
+    if (e.copy_b1) SW_HIP(hipMemcpyAsync(leader, run.b.bufs[1], size_t(n) * 4, hipMemcpyDeviceToDevice, run.s));
+    hipLaunchKernelGGL(k_state, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, run.s, leader, run.b.ids, state, n);
+    SW_LAUNCHED();
+    *rounds_exec = e.last;
+    if (st) {
+        const ElectTotals &tot = run.tot;
+        st->rounds_launched = sc.launched();
+        st->changes_total = tot.chg_sum;
+        st->gather_ms = tot.k_ms;
+        st->apply_ms = 0.0;
+        st->gather_launches = tot.timed_rounds;
+        st->active_total = tot.act_sum;
+        st->edges_total = tot.edge_sum;
+        st->dense_rounds = tot.dense_rounds;
+        st->bytes_total = tot.bytes;
+        st->sparse_ms = tot.sp_ms;
+        st->sparse_launches = tot.sp_launches;
+        st->sparse_bytes = tot.sp_bytes;
+        st->pair_launches = sc.pair_launches();
+    }
+    return e.converged ? SWARM_OK : SWARM_NOT_CONVERGED;
+}
+
 template <typename Off>
 int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, const int32_t *ids,
                int32_t *leader, uint8_t *state, int32_t max_rounds, int32_t mode,
@@ -1970,7 +2383,6 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
     SW_ARG(mode == SWARM_ELECT_DENSE || mode == SWARM_ELECT_FRONTIER, "unknown mode");
     SW_ARG(rounds_exec != nullptr, "rounds_exec is NULL");
     SW_ARG(n == 0 || (rp && ids && leader && state), "NULL array (col may be NULL only without edges)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (st) *st = swarm_elect_stats{};
     if (n == 0) {  // an empty swarm: round 1 changes nothing
         *rounds_exec = 1;
@@ -1978,386 +2390,40 @@ int elect_impl(swarm_ctx *ctx, int64_t n, const Off *rp, const int32_t *col, con
         if (st) st->rounds_launched = 1;
         return SWARM_OK;
     }
-    // 16-bit columns are checked before any round reads them (one pass over the columns, read back with
-    // the edge count): escaped columns or a foreign buffer are refused, never gathered through
-    SW_ARG(!c16 || !esc_registered(ctx, c16), "col16 holds swarm_graph_compact_escaped's columns (escapes)");
-    // SWARM_ELECT_TRUST_C16 with this ctx's record of the buffer: its columns and the edge count are known
-    const swarm_ctx::C16Built *rec = (trust_c16 && c16 && !hrp) ? c16_record(ctx, c16, rp, col, n) : nullptr;
-    Off e_total = 0;
-    if (rec) {
-        e_total = Off(rec->e_total);
-    } else {
-        unsigned c16_bad = 0;
-        if (c16) {
-            if (int rc = enqueue_col16_check<Off>(ctx, rp, c16, col, false, n, n, &c16_bad, s)) return rc;
-        }
-        SW_HIP(hipMemcpyAsync(&e_total, rp + n, sizeof(Off), hipMemcpyDeviceToHost, s));
-        SW_HIP(hipStreamSynchronize(s));
-        if (int rc = col16_verdict(c16_bad, "swarm_elect_compact")) return rc;
-    }
-    SW_ARG(e_total == 0 || col != nullptr, "col is NULL but the graph has edges");
-    // the int32-CSR kernels address with 32-bit byte offsets (gather_listed's ld4 / Col16::at32):
-    // 4-byte columns need < 2^30 edges, 2-byte ones < 2^31 (less a margin for the clamped offsets a
-    // window or a pass computes past its row's end) -- C5's 100M agents (1.6e9 edges) fit with them
-    const bool c16_only = c16 && !hrp && tuning().dense_flat;
-    const int64_t e_cap = c16_only ? (int64_t(1) << 31) - (int64_t(1) << 20) : (int64_t(1) << 30);
-    SW_ARG(sizeof(Off) == 8 || (n < (int64_t(1) << 30) && int64_t(e_total) < e_cap),
-           "int32 CSR supports < 2^30 agents and edges (< 2^31 - 2^20 edges with 16-bit columns): use "
-           "swarm_elect_i64 / swarm_elect_compact_i64");
-    if (hrp) {  // directed: the transpose must hold the same edges
-        Off h_total = 0;
-        SW_HIP(hipMemcpyAsync(&h_total, hrp + n, sizeof(Off), hipMemcpyDeviceToHost, s));
-        SW_HIP(hipStreamSynchronize(s));
-        SW_ARG(h_total == e_total, "hear_row_ptr[n] != row_ptr[n]: not the transpose of the graph");
-        SW_ARG(h_total == 0 || hcol != nullptr, "hear_col is NULL but the graph has edges");
-    }
-    int32_t *bufs[2] = {leader, nullptr};
-    SW_ALLOC(bufs[1], ctx, S_LEADER_B, size_t(n) * 4);
-    // The leader buffers start as copies of ids -- unless rounds 1 and 2 are both dense: round 1 then reads
-    // ids itself and writes every entry of bufs[1], round 2 every entry of bufs[0] = leader, and no later
-    // round reads anything older.  A call whose ids overlaps leader keeps the copies.
-    const bool aliased = ids < leader + n && leader < ids + n;
-    const bool skip_copy = tuning().skip_init_copy && !aliased &&
-                           (mode == SWARM_ELECT_DENSE || tuning().dense_rounds >= 2);
-    if (!skip_copy) SW_HIP(hipMemcpyAsync(leader, ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
-    Frontier f{};
-    unsigned long long *ring;
-    if (mode == SWARM_ELECT_FRONTIER) {
-        if (!skip_copy) SW_HIP(hipMemcpyAsync(bufs[1], ids, size_t(n) * 4, hipMemcpyDeviceToDevice, s));
-        int rc0 = frontier_alloc(ctx, n, n, bufs[0], bufs[1], &f, s);
-        if (rc0) return rc0;
-        ring = f.ring;
-        f.c16 = c16;
-    } else {
-        SW_ALLOC(ring, ctx, S_CHANGES, ring_bytes());
-        SW_HIP(hipMemsetAsync(ring, 0, ring_bytes(), s));
-        ctx->step_rows = ctx->step_all = 0;  // the stepper state is gone
-    }
-    constexpr int kMaxBatch = 256;
-    // the per-round totals land in mapped host memory, written by k_batch_totals itself, then the batch's
-    // epoch word after them (k_signal), which the host spins on
-    void *dmap = nullptr;
-    unsigned long long *hbuf =
-        static_cast<unsigned long long *>(mapped(ctx, size_t(kCounters) * 8 * kMaxBatch + 128, &dmap));
-    if (!hbuf) return SWARM_ERR_OOM;
-    unsigned long long *dtot = static_cast<unsigned long long *>(dmap);
-    unsigned long long *h_epoch = hbuf + size_t(kCounters) * kMaxBatch;
-    unsigned long long *d_epoch = dtot + size_t(kCounters) * kMaxBatch;
-    // a tag no counter value reaches, then the batch number (the word is shared with other calls)
-    const unsigned long long ep_tag = 0xE1EC7ull << 40;
-    unsigned long long ep = 0;
-    __atomic_store_n(h_epoch, 0ull, __ATOMIC_RELEASE);
+    ElectRun<Off> run{ctx, {n, rp, col, hrp, hcol, c16, rp2, c2, 0}, static_cast<hipStream_t>(stream), changes_host};
+    const bool frontier = mode == SWARM_ELECT_FRONTIER;
+    if (int rc = check_graph(ctx, run.g, trust_c16, run.s)) return rc;
+    if (int rc = setup_buffers(ctx, n, ids, leader, c16, frontier, run.s, &run.b)) return rc;
+    if (int rc = run.rb.open(ctx, run.b.ring, run.s)) return rc;
+    if (const char *pth = getenv("SWARM_ROUND_LOG")) run.rlog = fopen(pth, "w");
+    if (int rc = run.tm.open(timed, run.rlog != nullptr)) return rc;
 
-    int found = -1, t = 1, batch = 8, launched = 0;
-    std::vector<int64_t> hist;  // per-round change counts read so far (batch sizing, layout)
-    const StampMap il_map = stamp_map(n, true), ag_map = stamp_map(n, false);
-    const int64_t il_min = tuning().il_min_changes >= 0 ? tuning().il_min_changes
-                                                        : std::max<int64_t>(1, int64_t(8e-4 * double(n)));
-    StampMap rd_map = il_map;
-    int64_t act_sum = 0, edge_sum = 0, chg_sum = 0, dense_rounds = 0, sp_launches = 0;
-    double bytes = 0.0, sp_bytes = 0.0, sp_ms = 0.0;
-    std::vector<RoundKind> kinds(kMaxBatch);
-    std::vector<float> ktime(kMaxBatch);
-    // optional per-round timing: events before and after every round kernel
-    std::vector<hipEvent_t> ev;
-    double k_ms = 0;
-    int64_t timed_rounds = 0;
-    if (timed) {
-        ev.resize(2 * kMaxBatch + 2);
-        for (auto &x : ev) SW_HIP(hipEventCreate(&x));
-    }
-    struct EvFree {
-        std::vector<hipEvent_t> &v;
-        ~EvFree() { for (auto x : v) (void)hipEventDestroy(x); }
-    } ev_free{ev};
-    FILE *rlog = nullptr;  // SWARM_ROUND_LOG=path: one line per round (tuning aid)
-    if (const char *pth = getenv("SWARM_ROUND_LOG")) rlog = fopen(pth, "w");
-    struct LogClose {
-        FILE *&f;
-        ~LogClose() { if (f) fclose(f); }
-    } log_close{rlog};
-    // Look-ahead: each batch's counters are read back from a point kLook rounds before its end, so
-    // the GPU is still running the batch's last rounds while the host reads, decides the next batch
-    // and enqueues it (no idle gap at a batch boundary).  Rounds launched past convergence are
-    // guarded no-ops.  Per-round timing and the round log keep the plain read-at-the-end batches.
-    const int kLook = (timed || rlog) ? 0 : tuning().look;
-    int read_upto = 0;  // rounds whose counters the host has read
-    // the per-round counters of rounds (read_upto, tread], read back into hbuf: hist, stats, found
-    auto consume = [&](int tread) {
-        for (int r = read_upto + 1; r <= tread; ++r) {
-            const unsigned long long *rb = hbuf + size_t(r - read_upto - 1) * kCounters;
-            const int64_t c = int64_t(rb[C_CHG]);
-            hist.push_back(c);
-            const RoundKind kind = mode == SWARM_ELECT_DENSE ? RK_DENSE : plan_round(r);
-            const bool dn = kind == RK_DENSE || kind == RK_DENSE_MARK;
-            if (changes_host) changes_host[r - 1] = c;
-            const int64_t act = dn ? n : int64_t(rb[C_ACT]);
-            const int64_t ed = dn ? int64_t(e_total) : int64_t(rb[C_EDGE]);
-            act_sum += act;
-            edge_sum += ed;
-            chg_sum += c;
-            dense_rounds += dn ? 1 : 0;
-            const double rbytes = round_bytes(dn, n, int64_t(e_total), act, ed);
-            bytes += rbytes;
-            if (kind == RK_SPARSE) sp_bytes += rbytes;
-            if (rlog)
-                fprintf(rlog, "%d %lld %lld %lld %d %.2f\n", r, (long long)c, (long long)act, (long long)ed,
-                        int(kind), timed && r >= t ? ktime[r - t] * 1e3 : 0.0);
-            if (c == 0) {
-                found = r;
-                break;
-            }
-        }
-        read_upto = tread;
-    };
-    // the counters of rounds (read_upto, upto] read back and consumed (every launched round drained)
-    // per-round totals of rounds (read_upto, upto], reduced on device into mapped host memory, then the
-    // batch's epoch word: one launch (SWARM_FUSED_READBACK) or two
-    auto enqueue_totals = [&](int upto) -> int {
-        if (tuning().fused_readback) {
-            hipLaunchKernelGGL(k_batch_totals_signal, dim3(1), dim3(kReadbackThreads), 0, s, ring, read_upto + 1,
-                               upto - read_upto, dtot, d_epoch, ep_tag | ++ep);
-            SW_LAUNCHED();
-            return SWARM_OK;
-        }
-        hipLaunchKernelGGL(k_batch_totals, dim3(upto - read_upto), dim3(kWave), 0, s, ring, read_upto + 1, dtot);
-        SW_LAUNCHED();
-        hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, s, d_epoch, ep_tag | ++ep);
-        SW_LAUNCHED();
-        return SWARM_OK;
-    };
-    auto read_rounds = [&](int upto) -> int {
-        if (upto <= read_upto) return SWARM_OK;
-        if (int rc2 = enqueue_totals(upto)) return rc2;
-        if (int rc2 = wait_mapped_word(h_epoch, ep_tag | ep, s, "election read-back")) return rc2;
-        consume(upto);
-        return SWARM_OK;
-    };
-    int cleared_for = 0;  // the launch whose stamp clear the launch before it did in its own launch
-    // Pair rounds (gather_listed_pair's header): with a two-hop index, once the last read round changed fewer
-    // than pair_below agents, one single round marks two-hop rows (PF_MARK) and every launch behind it covers
-    // two rounds (PF_PAIR) -- a single one only where one round is left before max_rounds.  lc counts launches,
-    // lend[i] is the last round of launch i (lend[0] = 0): buffers and stamps follow lc, counters the round.
-    const bool pair_ok = rp2 && c2 && c16 && !hrp && sizeof(Off) == 4 && mode == SWARM_ELECT_FRONTIER && !rlog &&
-                         tuning().tail_wg == 0 && tuning().list_mask == kListDefault;
-    const double pair_below = tuning().pair_below >= 0 ? tuning().pair_below : 8.0 * tuning().sparse_blocks;
-    bool pair_mode = false;
-    int lc = 0;
-    int64_t pair_launches = 0;
-    std::vector<int> lend(1, 0);
-    int64_t tail_retry_below = INT64_MAX;  // the tail did not start: retry once the changes halve
-    // One-workgroup tail from round launched + 1: drain, collect the marked agents, run k_tail_wg, read its
-    // rounds' counters.  Leaves launched / rd_map where the frontier rounds go on.
-    auto tail_rounds = [&](int cap) -> int {
-        if (int rc2 = read_rounds(launched)) return rc2;
-        if (found > 0 || launched >= max_rounds) return SWARM_OK;
-        const int t0 = launched + 1;
-        const int t_end = std::min(max_rounds, t0 + 199);  // <= 200 rounds: one counter read-back
-        char *tb;
-        const size_t clk_words = tuning().tail_log ? 2 * 201 : 0;
-        SW_ALLOC(tb, ctx, S_LIST, 64 + size_t(kTailCap) * 4 + clk_words * 8);
-        unsigned *gcount = reinterpret_cast<unsigned *>(tb);
-        int32_t *glist = reinterpret_cast<int32_t *>(tb + 64);
-        unsigned long long *clk = clk_words ? reinterpret_cast<unsigned long long *>(tb + 64 + size_t(kTailCap) * 4)
-                                            : nullptr;
-        SW_HIP(hipMemsetAsync(gcount, 0, 4, s));
-        f.sm = rd_map;
-        const dim3 cgrid(grid_for(f.sm.M, 1, unsigned(tuning().sparse_blocks)));
-        if (f.sm.cshift == 9)  // small swarm: 512-stamp chunks (2 per thread)
-            hipLaunchKernelGGL((k_tail_collect<2>), cgrid, dim3(kBlock), 0, s, f, t0, glist, gcount, cap);
-        else
-            hipLaunchKernelGGL((k_tail_collect<kScan>), cgrid, dim3(kBlock), 0, s, f, t0, glist, gcount, cap);
-        SW_LAUNCHED();
-        const int64_t n16 = int64_t(2 * act_bytes(n)) / 16;
-        hipLaunchKernelGGL(k_tail_clear, dim3(grid_for(n16, kBlock, 2048)), dim3(kBlock), 0, s,
-                           reinterpret_cast<uint4 *>(f.act[0]), n16, gcount, cap);
-        SW_LAUNCHED();
-        f.wsm = ag_map;  // hand-back marks in agent order
-        // out[0..3] in mapped memory after the batch totals' epoch word
-        unsigned long long *h_out = h_epoch + 1, *d_out = d_epoch + 1;
-        const unsigned long long tep = (0x7A11ull << 40) | ++ep;
-        __atomic_store_n(&h_out[3], 0ull, __ATOMIC_RELEASE);
-        if (c16)
-            hipLaunchKernelGGL((k_tail_wg<Col16>), dim3(1), dim3(kTailThreads), 0, s,
-                               reinterpret_cast<const int32_t *>(rp), Col16{c16}, f, glist, gcount, t0, t_end, cap,
-                               d_out, tep, clk);
-        else
-            hipLaunchKernelGGL((k_tail_wg<Col32>), dim3(1), dim3(kTailThreads), 0, s,
-                               reinterpret_cast<const int32_t *>(rp), Col32{col}, f, glist, gcount, t0, t_end, cap,
-                               d_out, tep, clk);
-        SW_LAUNCHED();
-        if (int rc2 = wait_mapped_word(&h_out[3], tep, s, "one-workgroup tail")) return rc2;
-        const unsigned long long why = __atomic_load_n(&h_out[1], __ATOMIC_ACQUIRE);
-        const int last = int(__atomic_load_n(&h_out[0], __ATOMIC_ACQUIRE));
-        if (why == TAIL_NOT_STARTED) {
-            tail_retry_below = std::max<int64_t>(1, hist.back() / 2);
-            return SWARM_OK;
-        }
-        if (clk) {  // experiment aid: per-round microseconds (100 MHz wall clock) and marked agents
-            SW_HIP(hipStreamSynchronize(s));
-            std::vector<unsigned long long> hc(clk_words);
-            SW_HIP(hipMemcpy(hc.data(), clk, clk_words * 8, hipMemcpyDeviceToHost));
-            for (int r = t0; r < last; ++r)
-                fprintf(stderr, "[tail] round %d marked %llu us %.2f\n", r, hc[2 * (r - t0) + 1],
-                        double(hc[2 * (r - t0 + 1)] - hc[2 * (r - t0)]) / 100.0);
-        }
-        launched = last;
-        while (lc < launched) lend.push_back(++lc);  // (no pair rounds with the tail: a launch per round)
-        if (int rc2 = read_rounds(last)) return rc2;
-        rd_map = ag_map;  // the hand-back marks (if the run goes on)
-        batch = 8;
-        return SWARM_OK;
-    };
-    while (read_upto < max_rounds && found < 0) {
-        t = launched + 1;  // first round launched in this batch (> tend when only a read is left)
-        const int tend = std::min(max_rounds, launched + batch);
-        // read rounds (read_upto, tread]: at least one (the first batches are shorter than kLook)
-        const int tread = tend == max_rounds ? tend : std::max(read_upto + 1, tend - kLook);
-        int rc = 0;
-        auto enqueue_read = [&]() -> int { return enqueue_totals(tread); };
-        if (tread <= launched && (rc = enqueue_read())) return rc;
-        // timing: dense rounds (and every round when a per-round log is written) get an event pair
-        // each; a batch's run of back-to-back sparse rounds gets ONE pair around it -- events
-        // between every launch would add their own cost to each round (rocprof's per-dispatch
-        // durations are the reference for this figure)
-        int seg_n = 0;  // sparse launches inside this batch's segment
-        int last_end = launched;  // the last round launched (a batch's last pair may end one round past tend)
-        for (int r = t, step = 1; r <= tend; r += step) {
-            step = 1;
-            const bool sparse = mode == SWARM_ELECT_FRONTIER && plan_round(r) == RK_SPARSE;
-            const bool seg = timed && sparse && !rlog;
-            if (seg && seg_n++ == 0) SW_HIP(hipEventRecord(ev[2 * kMaxBatch], s));
-            hipEvent_t *e2 = (timed && !seg) ? &ev[2 * (r - t)] : nullptr;
-            if (e2) SW_HIP(hipEventRecord(e2[0], s));
-            if (mode == SWARM_ELECT_DENSE) {
-                kinds[r - t] = RK_DENSE;
-                rc = launch_dense_round<Off>(rp, col, (r == 1 && skip_copy) ? ids : bufs[(r - 1) & 1], bufs[r & 1], n, 0,
-                                             n, ring, nullptr, nullptr, StampMap{}, r, 1, s, nullptr, nullptr, c16);
-            } else if (r == 1 && skip_copy) {  // a dense round (dense_rounds >= 2) that reads ids
-                kinds[r - t] = plan_round(r);
-                Frontier f1 = f;
-                f1.L[0] = const_cast<int32_t *>(ids);
-                f1.sm = f1.wsm = il_map;
-                rc = launch_frontier_round<Off>(rp, col, f1, r, kinds[r - t], 1, s, hrp, hcol);
-            } else {
-                kinds[r - t] = plan_round(r);
-                // marks for round r+1: interleaved layout while rounds are busy (balance), agent
-                // order once they are sparse (locality of the few gathers)
-                f.sm = rd_map;
-                f.wsm = (hist.empty() || hist.back() >= il_min) ? il_map : ag_map;
-                RoundPlan pl{lc + 1, lc >= 2 ? lend[lc - 1] : 0, PF_SINGLE, tuning().pair_lanes, rp2, c2};
-                if (pair_ok && kinds[r - t] == RK_SPARSE) {
-                    if (!pair_mode && !hist.empty() && double(hist.back()) < pair_below) {
-                        pl.form = PF_MARK;
-                        pair_mode = true;
-                    } else if (pair_mode && r + 1 <= max_rounds) {
-                        pl.form = PF_PAIR;
-                        step = 2;
-                        ++pair_launches;
-                        if (r + 1 - t < kMaxBatch) kinds[r + 1 - t] = RK_SPARSE;
-                    }
-                }
-                rc = launch_frontier_round<Off>(rp, col, f, r, kinds[r - t], 1, s, hrp, hcol, &cleared_for,
-                                                pair_ok ? &pl : nullptr);
-                rd_map = f.wsm;
-            }
-            if (rc) return rc;
-            ++lc;
-            last_end = r + step - 1;
-            lend.push_back(last_end);
-            if (e2) SW_HIP(hipEventRecord(e2[1], s));
-            if (tread >= r && tread <= last_end && (rc = enqueue_read())) return rc;
-        }
-        if (seg_n) SW_HIP(hipEventRecord(ev[2 * kMaxBatch + 1], s));
-        launched = std::max(launched, last_end);
-        if ((rc = wait_mapped_word(h_epoch, ep_tag | ep, s, "election read-back"))) return rc;
-        if (timed) {  // kLook == 0: this batch's rounds are exactly the rounds read
-            SW_HIP(hipStreamSynchronize(s));
-            for (int r = t; r <= tend; ++r) {  // every launched round's kernel time (rocprof's view)
-                if (seg_n && kinds[r - t] == RK_SPARSE) continue;  // in the segment (a pair: both its rounds)
-                float x = 0;
-                SW_HIP(hipEventElapsedTime(&x, ev[2 * (r - t)], ev[2 * (r - t) + 1]));
-                k_ms += x;
-                ++timed_rounds;
-                if (kinds[r - t] == RK_SPARSE) {
-                    sp_ms += x;
-                    ++sp_launches;
-                }
-                ktime[r - t] = x;
-            }
-            if (seg_n) {
-                float x = 0;
-                SW_HIP(hipEventElapsedTime(&x, ev[2 * kMaxBatch], ev[2 * kMaxBatch + 1]));
-                k_ms += x;
-                sp_ms += x;
-                timed_rounds += seg_n;
-                sp_launches += seg_n;
-            }
-        }
-        consume(tread);
-        // a batch spans at most kRing/2 rounds of counter slots, look-ahead included (bookkeeping
-        // recycles the slot of round t - kRing/2 in round t)
-        // (pair rounds: one round of room for the pair that ends past its batch)
-        batch = next_round_batch(hist.data(), hist.size(), batch, kMaxBatch - kLook - (pair_ok ? 2 : 0));
-        // The switch to pair rounds happens at a batch's first round: a batch that is about to cross pair_below
-        // ends where the linear trend of the last 32 rounds crosses it (8 rounds at the least), and within a
-        // quarter above it (the curve is flat and noisy there at 10M agents: 20 changes per round of slope)
-        // batches are 16 rounds, so that the pairs do not start a long batch late.
-        if (pair_ok && !pair_mode && hist.size() >= 32 && double(hist.back()) >= pair_below) {
-            const double slope = double(hist[hist.size() - 32] - hist.back()) / 31.0;
-            if (slope > 0) {
-                const double rem = 1.1 * (double(hist.back()) - pair_below) / slope + 2.0;
-                batch = std::min(batch, rem < 8.0 ? 8 : rem > double(kMaxBatch) ? kMaxBatch : int(rem));
-            }
-            if (double(hist.back()) < 1.25 * pair_below) batch = std::min(batch, 16);
-        }
-        // the one-workgroup tail (opt-in experiment): once the last read round's risers x 4 fit its list (the
-        // marked agents of a tail round are ~3x the previous round's risers at 100k-10M agents; a list that
-        // does not fit is caught by the collect), with short batches once that is near, so that the switch
-        // is not a long batch late
-        const int cap = tuning().tail_wg;
-        if (cap > 0 && !hist.empty() && hist.back() * 4 <= 8 * int64_t(cap)) batch = std::min(batch, 8);
-        if (cap > 0 && found < 0 && mode == SWARM_ELECT_FRONTIER && !hrp && !timed && !rlog && sizeof(Off) == 4 &&
-            !hist.empty() && hist.back() > 0 && hist.back() * 4 <= cap && hist.back() < tail_retry_below &&
-            launched < max_rounds && plan_round(launched + 1) == RK_SPARSE) {
-            if ((rc = tail_rounds(cap))) return rc;
+    const Tuning &tu = tuning();
+    ScheduleParams p;
+    p.max_rounds = max_rounds;
+    p.dense_rounds = tu.dense_rounds;
+    // Look-ahead: rounds launched past convergence are guarded no-ops.  Per-round timing and the round log
+    // keep the plain read-at-the-end batches.
+    p.look = (timed || run.rlog) ? 0 : tu.look;
+    p.frontier = frontier;
+    p.pair_ok = rp2 && c2 && c16 && !hrp && sizeof(Off) == 4 && frontier && !run.rlog && tu.tail_wg == 0 &&
+                tu.list_mask == kListDefault;
+    p.pair_below = tu.pair_below >= 0 ? tu.pair_below : 8.0 * tu.sparse_blocks;
+    p.tail_cap = tu.tail_wg;
+    p.tail_ok = !hrp && !timed && !run.rlog && sizeof(Off) == 4;
+    p.max_batch = kMaxBatch;
+    p.ring = kRing;
+    p.skip_copy = run.b.skip_copy;
+    p.doubling_only = batch_doubling_only();
+    p.il_min = il_min_for(n, tu.il_min_changes);
+    ElectSchedule sc(p);
+    while (sc.running()) {
+        if (int rc = run_batch(run, sc)) return rc;
+        if (sc.tail_due()) {
+            if (int rc = tail_rounds(run, sc, tu.tail_wg)) return rc;
         }
     }
-    const int last = found > 0 ? found : max_rounds;
-    // The newest buffer is bufs[lc & 1] (lc launches were issued).  After a launch whose rounds all changed
-    // nothing both buffers hold the final state (dense and frontier alike).  A pair launch whose first round
-    // changed something and whose second nothing leaves it in the buffer it wrote only; the launch behind it
-    // (not guarded: its guard word is an earlier, non-zero round's) rewrites the other one.  (Without the
-    // initial copies a run that ends with round 1 has written bufs[1] only, zero changes or not.)
-    bool newest_only = found < 0;
-    int lfin = lc;  // the launch that wrote the final state
-    if (found > 0) {
-        lfin = int(std::lower_bound(lend.begin(), lend.end(), found) - lend.begin());
-        newest_only = lfin == lc && lfin >= 1 && lend[lfin - 1] + 1 != found;
-    }
-    if ((newest_only && (lfin & 1)) || (skip_copy && last == 1)) {
-        SW_HIP(hipMemcpyAsync(leader, bufs[1], size_t(n) * 4, hipMemcpyDeviceToDevice, s));
-    }
-    hipLaunchKernelGGL(k_state, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, leader,
-                       ids, state, n);
-    SW_LAUNCHED();
-    *rounds_exec = last;
-    if (st) {
-        st->rounds_launched = launched;
-        st->changes_total = chg_sum;
-        st->gather_ms = k_ms;
-        st->apply_ms = 0.0;
-        st->gather_launches = timed_rounds;
-        st->active_total = act_sum;
-        st->edges_total = edge_sum;
-        st->dense_rounds = dense_rounds;
-        st->bytes_total = bytes;
-        st->sparse_ms = sp_ms;
-        st->sparse_launches = sp_launches;
-        st->sparse_bytes = sp_bytes;
-        st->pair_launches = pair_launches;
-    }
-    return found > 0 ? SWARM_OK : SWARM_NOT_CONVERGED;
+    return finish(run, sc, state, rounds_exec, st);
 }
 
 }  // namespace
@@ -2399,10 +2465,10 @@ int frontier_round_stepper(swarm_ctx *ctx, int t, const int32_t *rp, const int32
 // Whether round t of the frontier stepper is a dense sweep (its active / edge counters are not kept).
 bool frontier_round_dense(int t) { return plan_round(t) != RK_SPARSE; }
 
-// The interleaved -> agent-order switch point of the stamp layout for an n-agent swarm (elect_impl's
-// il_min; the sharded C loop compares the global changes against it for the global agent count).
+// The interleaved -> agent-order switch point of the stamp layout for an n-agent swarm (il_min_for, the rule
+// elect_impl's schedule uses; the sharded C loop compares the global changes against it for the global agent count).
 int64_t frontier_il_min(int64_t n) {
-    return tuning().il_min_changes >= 0 ? tuning().il_min_changes : std::max<int64_t>(1, int64_t(8e-4 * double(n)));
+    return il_min_for(n, tuning().il_min_changes);
 }
 
 int frontier_ghosts_both(swarm_ctx *ctx, int t, const int32_t *rp, const int32_t *col, int64_t b_lo, int64_t n_lo,

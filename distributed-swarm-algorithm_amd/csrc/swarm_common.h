@@ -288,28 +288,27 @@ int moving_board_restore_if_refused(swarm_board *b, const unsigned long long *st
 
 namespace swarm {
 
-// Rounds in the next batch of an election loop (launched before the host reads their counts):
-// double up to max_batch, but no more than ~1.5x the rounds a linear extrapolation of the last
-// 32 per-round change counts leaves before zero -- rounds launched past convergence are wasted
-// no-op launches (~8 us each at 10M agents; 164 of them at C3, 106 at C2 with pure doubling).
-inline int next_round_batch(const int64_t *hist, size_t nh, int batch, int max_batch) {
-    int b = batch * 2 < max_batch ? batch * 2 : max_batch;
-    constexpr size_t k = 32;
-    static const bool doubling_only = [] {  // SWARM_BATCH_DOUBLING=1: plain doubling (A/B aid)
+// The election's entry points for comm.hip (the RCCL round loop), defined in elect.hip: one stepper round, the
+// ghost update of both borders, the device per-round totals (kElectCounters each) of rounds t0..t1, the check
+// of the stepper's 16-bit columns, the stamp layout's switch point for an n-agent swarm (elect_schedule.h,
+// il_min_for) and whether stepper round t is a dense sweep.
+int frontier_round_stepper(swarm_ctx *ctx, int t, const int32_t *rp, const int32_t *col, int32_t *L0,
+                           int32_t *L1, hipStream_t s);
+int frontier_ghosts_both(swarm_ctx *ctx, int t, const int32_t *rp, const int32_t *col, int64_t b_lo, int64_t n_lo,
+                         const int32_t *in_lo, int64_t b_hi, int64_t n_hi, const int32_t *in_hi, int32_t *L0,
+                         int32_t *L1, hipStream_t s);
+int frontier_round_totals(swarm_ctx *ctx, int t0, int t1, unsigned long long *dtot, hipStream_t s);
+int frontier_check_compact(swarm_ctx *ctx, const int32_t *rp, const int32_t *col, hipStream_t s);
+int64_t frontier_il_min(int64_t n);
+bool frontier_round_dense(int t);
+
+// SWARM_BATCH_DOUBLING=1: the election loops' batches double plainly (next_round_batch's A/B aid)
+inline bool batch_doubling_only() {
+    static const bool on = [] {
         const char *e = getenv("SWARM_BATCH_DOUBLING");
         return e && e[0] == '1';
     }();
-    if (nh >= k && !doubling_only) {
-        const double slope = double(hist[nh - k] - hist[nh - 1]) / double(k - 1);
-        if (slope > 0) {
-            // rounds left on the linear trend, + 25 % and 4 rounds of margin: an overshoot costs one
-            // no-op launch per round (~6 µs), an undershoot one more host round trip
-            const double rem = 1.25 * double(hist[nh - 1]) / slope + 4.0;
-            const int p = rem < 8.0 ? 8 : (rem > double(max_batch) ? max_batch : int(rem + 0.5));
-            if (p < b) b = p;
-        }
-    }
-    return b;
+    return on;
 }
 
 // Grid for a grid-stride kernel over `work` items with `per_block` items per block pass.

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 
-# swarm_elect_compact's edge cap with 16-bit columns (elect.hip elect_impl: 32-bit byte offsets into
+# swarm_elect_compact's edge cap with 16-bit columns (elect.hip check_graph: 32-bit byte offsets into
 # the int16 columns, less a margin for the clamped offsets past a row's end)
 _C16_EDGE_CAP = (1 << 31) - (1 << 20)
 
