@@ -1464,10 +1464,26 @@ __global__ __launch_bounds__(kBlock) void k_board_sender_bytes(int64_t n2, const
 // k_task_conflicts' walk over sparse rows: for every task of a heard sender's conflict row the winner is looked
 // up in the sender's table row (no entry: -1, everyone LOCKED) and the receiver's status row upserted; the last
 // conflict in walk order decides.  No thread of this launch writes a table or a conflict row.
-template <class Ch>
+// The lifetime policy (contract U1-A.3) stands beside the channel policy: on a board with lifetimes a
+// conflict about a task absent at this tick writes nothing (agent.py:332, 335: `if task_id in self.tasks`); the
+// tick's presence bytes come from the key pass of the board's lists (task_board.hip).
+struct NoLife {
+    static constexpr bool kLife = false;
+};
+struct Lifetimes {
+    static constexpr bool kLife = true;
+    const uint8_t *present;  // by task index, this tick
+    __device__ bool absent(int32_t task) const { return present[task] == 0; }
+};
+// Both policies as one kernel argument: an empty policy takes no room (empty bases), so the NoLife kernels keep
+// the argument layout they had with the channel alone.
+template <class Ch, class Lf>
+struct BoardPolicy : Ch, Lf {};
+
+template <class Ch, class Lf>
 __global__ __launch_bounds__(kBlock) void k_board_conflicts(int64_t n, int64_t t, const int32_t *__restrict__ ids,
                                                            const uint2 *__restrict__ rec, Radio w, BoardTick k,
-                                                           Ch ch) {
+                                                           BoardPolicy<Ch, Lf> pl) {
     if (w.st[0] != 0) return;
     for (int64_t q0 = int64_t(blockIdx.x) * kBlock + threadIdx.x; q0 < n; q0 += int64_t(gridDim.x) * kBlock) {
         const double2 p = w.psort[q0];
@@ -1493,7 +1509,7 @@ __global__ __launch_bounds__(kBlock) void k_board_conflicts(int64_t n, int64_t t
             const double ex = p.x - s.x, ey = p.y - s.y;
             if (!(ex * ex + ey * ey <= w.r2)) return;
             if constexpr (Ch::kLossy)
-                if (ch.dropped(t, ids[j], me)) return;
+                if (pl.dropped(t, ids[j], me)) return;
             const int32_t *crow = k.conflict_in + int64_t(j) * k.Kt;
             const int32_t *tt = k.tab_task + int64_t(j) * k.Kt;
             const int32_t *tw = k.tab_winner + int64_t(j) * k.Kt;
@@ -1503,6 +1519,8 @@ __global__ __launch_bounds__(kBlock) void k_board_conflicts(int64_t n, int64_t t
             for (int c = 0; c < k.Kt; ++c) {
                 const int32_t a = crow[c];
                 if (a < 0) break;
+                if constexpr (Lf::kLife)
+                    if (pl.absent(a)) continue;
                 const int at = row_lower(tt, nt, a, 0);
                 const int32_t win = at < nt && tt[at] == a ? tw[at] : -1;
                 // ASSIGNED (3) for the winner, LOCKED (2) for everyone else
@@ -2065,7 +2083,13 @@ struct BoardState {
         hipLaunchKernelGGL(k_radio_outbox<true>, grid, dim3(kBlock), 0, s, r.n, bt.sb_in, rs.rw, bt.cell_claim,
                            bt.cell_conf);
         SW_LAUNCHED();
-        hipLaunchKernelGGL(k_board_conflicts<Ch>, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec, rs.rw, bt, ch);
+        // (contract U1-A) a board with lifetimes: conflicts about the tasks absent this tick write nothing
+        if (b.alive())
+            hipLaunchKernelGGL((k_board_conflicts<Ch, Lifetimes>), grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec,
+                               rs.rw, bt, BoardPolicy<Ch, Lifetimes>{ch, Lifetimes{b.present}});
+        else
+            hipLaunchKernelGGL((k_board_conflicts<Ch, NoLife>), grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, f.rec,
+                               rs.rw, bt, BoardPolicy<Ch, NoLife>{ch, NoLife{}});
         SW_LAUNCHED();
         hipLaunchKernelGGL(k_tick_radio_board<Ch>, grid, dim3(kBlock), 0, s, r.n, k.t, r.ids, k.pos, f, rs.rw,
                            k.ob_out, r.dt, r.timeout, r.jitter, r.seed, k.cnt, bt, ch);
@@ -2353,7 +2377,11 @@ int run_ticks(const TickRun &r) {
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;
         if (radio) rs.bind(ls);
         // (contract U1-M) the cell lists of Q_{t-1} before the tick's launches, the advance after them
-        if (boarded && r.mboard && (rc = moving_board_tick(r.mboard, s))) return rc;
+        if (boarded && r.mboard && (rc = moving_board_tick(r.mboard, t, s))) return rc;
+        // (contract U1-A) a retiring tick: the status entries of the tasks absent at t leave their rows first
+        if (boarded && r.mboard && moving_board_retires(r.mboard, r.t0, t) &&
+            (rc = moving_board_retire(r.mboard, ls.st, r.n, r.bstate->Ks, r.bstate->status, s)))
+            return rc;
         auto window_tick = [&](auto ch) {
             return boarded  ? bs.launch(r, f, k, rs, ls.st, ch, s)
                    : tasked ? ts.launch(r, f, k, rs, ch, s)
@@ -2590,7 +2618,10 @@ static int board_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos
     r.mboard = mboard;
     r.bstate = state;
     r.overflow = overflow;
-    return run_loop(kLoopRadio, r);
+    const int rc = run_loop(kLoopRadio, r);
+    // (contract U1-A.7) the first tick of a call that ran has retired: a refused call keeps nothing, that too
+    if (rc == SWARM_OK && mboard && n > 0 && ticks > 0 && r.boarded()) mboard->life_fresh = false;
+    return rc;
 }
 
 int swarm_update_loop_board(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos, double *pos_prev,

@@ -155,6 +155,13 @@ struct swarm_board {
     void *cub_tmp = nullptr;          // device: hipCUB's temporary storage
     size_t cap_cells = 0, cap_tmp = 0;  // what the two buffers above hold
     swarm::Grid call_g{};             // the call's grid
+    // Lifetimes (contract U1-A; task_life.h): one window of absolute ticks per task, on a moving board
+    // only.  `present` is rewritten by every tick's key pass; the host keeps the schedule of retiring ticks.
+    int64_t *life_open = nullptr, *life_close = nullptr;  // device: T each; NULL: every task always present
+    uint8_t *present = nullptr;                           // device: T, the tick's presence by task index
+    std::vector<int64_t> close_ticks;                     // the closing ticks, ascending, each once
+    bool life_fresh = false;  // set or changed, and no call has run since: the next call's first tick retires
+    bool alive() const { return life_open != nullptr; }
 };
 
 struct swarm_ctx {
@@ -253,7 +260,12 @@ inline bool live_board(const swarm_ctx *ctx, const swarm_board *b) {
 // advance, nothing once the stop word is set; at the end both lists back to their entry bytes if it is.
 int moving_board_box(swarm_board *b, double dt, int32_t ticks, hipStream_t s);
 int moving_board_begin(swarm_board *b, hipStream_t s);
-int moving_board_tick(swarm_board *b, hipStream_t s);
+int moving_board_tick(swarm_board *b, int64_t t, hipStream_t s);
+// (contract U1-A) does tick t of a call that starts after tick t0 retire; the retire pass over n status rows of Ks
+// slots (after moving_board_tick(t): it reads the tick's presence bytes); a call that ran is no longer the first.
+bool moving_board_retires(const swarm_board *b, int64_t t0, int64_t t);
+int moving_board_retire(const swarm_board *b, const unsigned long long *st, int64_t n, int32_t Ks, int32_t *status,
+                        hipStream_t s);
 int moving_board_advance(swarm_board *b, const unsigned long long *st, double dt, hipStream_t s);
 int moving_board_restore_if_refused(swarm_board *b, const unsigned long long *st, hipStream_t s);
 

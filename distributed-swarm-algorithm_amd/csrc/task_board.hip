@@ -9,6 +9,7 @@
 #include "binning.h"
 #include "swarm_common.h"
 #include "task_grid.h"
+#include "task_life.h"
 #include "task_motion.h"
 #include "utility.h"
 
@@ -19,7 +20,8 @@ namespace {
 // Frees everything a board owns; the struct itself stays, an empty board.
 void release_board(swarm_board *b) {
     void *const dev[] = {b->tpos,    b->treq,    b->cell_off, b->sxy,     b->sir,     b->verdict, b->lag,    b->vel,
-                         b->entry,   b->box,     b->keys[0],  b->keys[1], b->vals[0], b->vals[1], b->dyn_off, b->cub_tmp};
+                         b->entry,   b->box,     b->keys[0],  b->keys[1], b->vals[0], b->vals[1], b->dyn_off, b->cub_tmp,
+                         b->life_open, b->life_close, b->present};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (b->verdict_host) (void)hipHostFree(b->verdict_host);
@@ -173,6 +175,95 @@ __global__ __launch_bounds__(kBlock) void k_task_restore(const unsigned long lon
     }
 }
 
+// ---- lifetimes (contract U1-A) ----
+//
+// k_cell_keys with the presence predicate (task_life.h): a task absent at tick t takes the key `ncells`, one past
+// the last cell, so the stable sort puts it behind every cell's run and the offsets search -- off[ncells] is the
+// first sorted position whose key is >= ncells -- leaves it in no run: the tick's kernels are never offered it.
+// The same pass writes the tick's presence bytes, which the retire pass and the conflict walk read.
+__global__ __launch_bounds__(kBlock) void k_cell_keys_life(const double2 *__restrict__ pos, int64_t T, Grid g,
+                                                          const int64_t *__restrict__ open,
+                                                          const int64_t *__restrict__ close, int64_t t,
+                                                          uint32_t *__restrict__ keys, int32_t *__restrict__ vals,
+                                                          uint8_t *__restrict__ present) {
+    for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < T; i += int64_t(gridDim.x) * kBlock) {
+        const double2 p = pos[i];
+        const int64_t cx = cell_coord(p.x, g.xmin, g.inv_cell, g.ncx);
+        const int64_t cy = cell_coord(p.y, g.ymin, g.inv_cell, g.ncy);
+        const bool in = task_present(open[i], close[i], t);
+        keys[i] = uint32_t(in ? cy * g.ncx + cx : g.ncx * g.ncy);
+        vals[i] = int32_t(i);
+        present[i] = uint8_t(in);
+    }
+}
+
+// The retire pass (contract U1-A.7): the status entries whose task is absent this tick leave their rows, the
+// entries behind them move down, the freed slots become -1 -- a canonical row again.  2^lg lanes share a row (the
+// least power of two that holds Ks, 64 at most), so a wave takes 64 >> lg rows at once and its loads are
+// consecutive 4-byte words; a longer row is walked in chunks of 64 and left at the first chunk that is not full
+// (the fillers are behind the entries).  The ranks come from one ballot per chunk.  In place: a chunk's stores go
+// to slots at or below the slots it has loaded, all loaded before the ballot that ranks them.  A lane stores only
+// where the slot's value changes, so a row that loses nothing is not written.  Nothing once the stop word is set.
+// Rows of at most 64 slots -- one chunk -- are taken kRetireTurn groups a turn, every group's loads issued before
+// the first ballot: with one 256-byte load in flight per wave the pass ran at 29 % of the copy rate.
+constexpr int kRetireTurn = 4;
+
+__global__ __launch_bounds__(kBlock) void k_board_retire(const unsigned long long *__restrict__ st, int64_t n,
+                                                        int32_t Ks, int32_t lg, int32_t T,
+                                                        const uint8_t *__restrict__ present,
+                                                        int32_t *__restrict__ status) {
+    if (st[0] != 0) return;  // uniform over the grid: written by an earlier kernel of the stream
+    const int L = 1 << lg, lane = threadIdx.x & (kWave - 1), sub = lane >> lg, lig = lane & (L - 1);
+    const int64_t per = kWave >> lg;  // rows per wave
+    const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> 6, nwaves = int64_t(gridDim.x) * (kBlock >> 6);
+    const uint64_t gm = lg == 6 ? ~0ull : ((1ull << L) - 1) << (sub * L);  // the lanes of this lane's row
+    const uint64_t below = gm & ((1ull << lane) - 1);
+    if (Ks <= kWave) {  // one chunk per row: kRetireTurn row groups a turn, all of them loaded before the first is ranked
+        const int64_t step = nwaves * per;
+        for (int64_t r0 = wave * per; r0 < n; r0 += kRetireTurn * step) {  // (uniform over the wave)
+            int32_t e[kRetireTurn];
+            bool keep[kRetireTurn];
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) {
+                const int64_t row = r0 + u * step + sub;
+                e[u] = row < n && lig < Ks ? status[row * Ks + lig] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) keep[u] = e[u] >= 0 && (e[u] >> 2) < T && present[e[u] >> 2] != 0;
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) {
+                const uint64_t mk = __ballot(keep[u]), mv = __ballot(e[u] >= 0);
+                if (mk == mv) continue;  // (uniform) no row of the group loses anything
+                const int at = __popcll(mk & below), kept = __popcll(mk & gm), seen = __popcll(mv & gm);
+                const int64_t base = (r0 + u * step + sub) * Ks;  // (a lane that stores holds an entry: its row exists)
+                if (keep[u] && at != lig) status[base + at] = e[u];
+                if (lig >= kept && lig < seen) status[base + lig] = -1;
+            }
+        }
+        return;
+    }
+    for (int64_t r0 = wave * per; r0 < n; r0 += nwaves * per) {  // (uniform over the wave)
+        const int64_t row = r0 + sub;
+        const bool live = row < n;
+        int32_t *rp = status + (live ? row : 0) * Ks;
+        int kept = 0, seen = 0;
+        for (int c = 0; c < Ks; c += L) {
+            const int idx = c + lig;
+            const int32_t e = live && idx < Ks ? rp[idx] : -1;
+            const bool valid = e >= 0;
+            const bool keep = valid && (e >> 2) < T && present[e >> 2] != 0;
+            const uint64_t mk = __ballot(keep), mv = __ballot(valid);
+            const int at = kept + __popcll(mk & below);
+            if (keep && at != idx) rp[at] = e;
+            kept += __popcll(mk & gm);
+            const int nv = __popcll(mv & gm);
+            seen += nv;
+            if (lg == 6 && nv < kWave) break;  // one row per wave: uniform
+        }
+        for (int q = kept + lig; q < seen; q += L) rp[q] = -1;
+    }
+}
+
 int sort_end_bit(int64_t ncells) {
     int b = 1;
     while (b < 32 && (int64_t(1) << b) < ncells) ++b;
@@ -206,20 +297,28 @@ int size_buffers(swarm_board *b, int64_t ncells, hipStream_t s) {
     size_t sort_bytes = 0;
     if (b->T)
         SW_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, b->keys[0], b->keys[1], b->vals[0], b->vals[1],
-                                                  int(b->T), 0, sort_end_bit(ncells), s));
+                                                  int(b->T), 0, sort_end_bit(ncells + 1), s));
     return grow(&b->cub_tmp, &b->cap_tmp, sort_bytes);
 }
 
-// The cell-sorted copy of `cur` on grid g, queued on s (size_buffers has run for g's cell count).
-int build_lists(swarm_board *b, const Grid &g, hipStream_t s) {
+// The cell-sorted copy of `cur` on grid g, queued on s (size_buffers has run for g's cell count).  tick (NULL:
+// every task): the tick whose present tasks the lists hold, on a board with lifetimes (contract U1-A) -- the sort
+// then covers the key of the absent, `ncells`.
+int build_lists(swarm_board *b, const Grid &g, const int64_t *tick, hipStream_t s) {
     const int64_t T = b->T, ncells = g.ncx * g.ncy;
+    const bool life = tick && b->alive();
     if (T) {
-        hipLaunchKernelGGL(k_cell_keys, dim3(grid_for(T, kBlock, 8192)), dim3(kBlock), 0, s,
-                           reinterpret_cast<const double2 *>(b->tpos), T, g, b->keys[0], b->vals[0]);
+        if (life)
+            hipLaunchKernelGGL(k_cell_keys_life, dim3(grid_for(T, kBlock, 8192)), dim3(kBlock), 0, s,
+                               reinterpret_cast<const double2 *>(b->tpos), T, g, b->life_open, b->life_close, *tick,
+                               b->keys[0], b->vals[0], b->present);
+        else
+            hipLaunchKernelGGL(k_cell_keys, dim3(grid_for(T, kBlock, 8192)), dim3(kBlock), 0, s,
+                               reinterpret_cast<const double2 *>(b->tpos), T, g, b->keys[0], b->vals[0]);
         SW_LAUNCHED();
         size_t tmp = b->cap_tmp;
         SW_HIP(hipcub::DeviceRadixSort::SortPairs(b->cub_tmp, tmp, b->keys[0], b->keys[1], b->vals[0], b->vals[1],
-                                                  int(T), 0, sort_end_bit(ncells), s));
+                                                  int(T), 0, sort_end_bit(ncells + (life ? 1 : 0)), s));
     }
     hipLaunchKernelGGL(k_cell_offsets_search, dim3(grid_for(ncells + 1, kBlock, 8192)), dim3(kBlock), 0, s, b->keys[1],
                        T, ncells, b->dyn_off);
@@ -317,7 +416,23 @@ int moving_board_begin(swarm_board *b, hipStream_t s) {
     return SWARM_OK;
 }
 
-int moving_board_tick(swarm_board *b, hipStream_t s) { return build_lists(b, b->call_g, s); }
+int moving_board_tick(swarm_board *b, int64_t t, hipStream_t s) { return build_lists(b, b->call_g, &t, s); }
+
+bool moving_board_retires(const swarm_board *b, int64_t t0, int64_t t) {
+    return b->alive() && task_tick_retires(b->close_ticks, b->life_fresh && t == t0 + 1, t);
+}
+
+int moving_board_retire(const swarm_board *b, const unsigned long long *st, int64_t n, int32_t Ks, int32_t *status,
+                        hipStream_t s) {
+    int lg = 0;
+    while (lg < 6 && (1 << lg) < Ks) ++lg;
+    int64_t waves = (n + (kWave >> lg) - 1) / (kWave >> lg);
+    if (Ks <= kWave) waves = (waves + kRetireTurn - 1) / kRetireTurn;
+    hipLaunchKernelGGL(k_board_retire, dim3(grid_for(waves * kWave, kBlock, 16384)), dim3(kBlock), 0, s, st, n, Ks, lg,
+                       int32_t(b->T), b->present, status);
+    SW_LAUNCHED();
+    return SWARM_OK;
+}
 
 int moving_board_advance(swarm_board *b, const unsigned long long *st, double dt, hipStream_t s) {
     hipLaunchKernelGGL(k_task_advance, dim3(grid_for(b->T, kBlock, 4096)), dim3(kBlock), 0, s, st, b->T,
@@ -433,6 +548,85 @@ int swarm_board_set_velocities(swarm_ctx *ctx, swarm_board *board, const double 
     return SWARM_OK;
 }
 
+int swarm_board_set_lifetimes(swarm_ctx *ctx, swarm_board *board, const int64_t *open_tick, const int64_t *close_tick,
+                              void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr && board != nullptr, "ctx or board is NULL");
+    SW_ARG((open_tick == nullptr) == (close_tick == nullptr), "open_tick and close_tick: both arrays, or both NULL");
+    SW_ARG(live_board(ctx, board), "the board is not a live board of this ctx");
+    SW_ARG(board->moving, "lifetimes need a moving board (swarm_board_create_moving; NULL velocities: at rest)");
+    if (!ctx_on_current_device(ctx)) return SWARM_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    swarm_board *b = board;
+    if (!open_tick) {  // no lifetimes: the board as it was made
+        SW_HIP(hipDeviceSynchronize());  // queued work may still read them
+        void *const dev[] = {b->life_open, b->life_close, b->present};
+        for (void *p : dev)
+            if (p) SW_HIP(hipFree(p));
+        b->life_open = b->life_close = nullptr;
+        b->present = nullptr;
+        b->close_ticks.clear();
+        b->life_fresh = false;
+        return SWARM_OK;
+    }
+    const size_t T = size_t(b->T), rows = T ? T : 1;
+    std::vector<int64_t> h_open, h_close, closes;
+    try {
+        h_open.resize(rows);
+        h_close.resize(rows);
+        if (T) {  // (device or host arrays)
+            SW_HIP(hipMemcpyAsync(h_open.data(), open_tick, T * 8, hipMemcpyDefault, s));
+            SW_HIP(hipMemcpyAsync(h_close.data(), close_tick, T * 8, hipMemcpyDefault, s));
+            SW_HIP(hipStreamSynchronize(s));
+        }
+        int64_t bad = -1;
+        switch (task_life_check(b->T, h_open.data(), h_close.data(), &bad)) {
+        case kTaskLifeOk:
+            break;
+        case kTaskLifeNegative:
+            set_error("invalid argument: task %lld has a negative open or close tick", static_cast<long long>(bad));
+            return SWARM_ERR_ARG;
+        default:
+            set_error("invalid argument: task %lld opens after it closes", static_cast<long long>(bad));
+            return SWARM_ERR_ARG;
+        }
+        closes = task_close_ticks(b->T, h_close.data());
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory for %zu lifetimes", T);
+        return SWARM_ERR_OOM;
+    }
+    if (!b->life_open) {  // all three or none: a failure leaves the board without lifetimes
+        int64_t *o = nullptr, *c = nullptr;
+        uint8_t *p = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&o), rows * 8) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&c), rows * 8) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&p), rows) != hipSuccess) {
+            (void)hipGetLastError();
+            if (o) (void)hipFree(o);
+            if (c) (void)hipFree(c);
+            set_error("out of device memory for %zu lifetimes", T);
+            return SWARM_ERR_OOM;
+        }
+        b->life_open = o, b->life_close = c, b->present = p;
+    }
+    if (T) {
+        SW_HIP(hipMemcpyAsync(b->life_open, h_open.data(), T * 8, hipMemcpyHostToDevice, s));
+        SW_HIP(hipMemcpyAsync(b->life_close, h_close.data(), T * 8, hipMemcpyHostToDevice, s));
+        SW_HIP(hipStreamSynchronize(s));
+    }
+    b->close_ticks = std::move(closes);
+    b->life_fresh = true;
+    return SWARM_OK;
+}
+
+int swarm_board_lifetimes(const swarm_board *board, const int64_t **open_tick, const int64_t **close_tick) {
+    using namespace swarm;
+    SW_ARG(board != nullptr && open_tick != nullptr && close_tick != nullptr, "board, open_tick or close_tick is NULL");
+    *open_tick = board->life_open;
+    *close_tick = board->life_close;
+    return SWARM_OK;
+}
+
 int swarm_board_positions(const swarm_board *board, const double **cur, const double **lag) {
     using namespace swarm;
     SW_ARG(board != nullptr && cur != nullptr && lag != nullptr, "board, cur or lag is NULL");
@@ -481,7 +675,7 @@ int swarm_board_refresh(swarm_ctx *ctx, swarm_board *board, swarm_board_desc *in
             const int64_t ncells = g.ncx * g.ncy;
             off.resize(size_t(ncells) + 1);
             if ((rc = size_buffers(b, ncells, s))) return rc;
-            if ((rc = build_lists(b, g, s))) return rc;
+            if ((rc = build_lists(b, g, nullptr, s))) return rc;
             SW_HIP(hipMemcpyAsync(off.data(), b->dyn_off, off.size() * 4, hipMemcpyDeviceToHost, s));
             if (T) SW_HIP(hipMemcpyAsync(idx.data(), b->vals[1], T * 4, hipMemcpyDeviceToHost, s));
             SW_HIP(hipStreamSynchronize(s));

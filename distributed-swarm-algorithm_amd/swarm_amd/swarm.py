@@ -166,6 +166,34 @@ def _board_velocities(v, T):
     return vel
 
 
+LIFE_FOREVER = np.iinfo(np.int64).max
+
+
+def _board_lifetimes(open_tick, close_tick, T):
+    """set_task_board / set_board_lifetimes: the (T,) int64 windows of open_tick / close_tick, each (T,) ints or a
+    scalar; None for open_tick is tick 0, for close_tick never (contract U1-A).  (None, None): no lifetimes."""
+    if open_tick is None and close_tick is None:
+        return None
+    out = []
+    for name, v, default in (("open_tick", open_tick, 0), ("close_tick", close_tick, LIFE_FOREVER)):
+        a = np.asarray(default if v is None else v)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be integer ticks, got dtype {a.dtype}")
+        if a.dtype.kind == "u" and a.size and int(a.max()) > LIFE_FOREVER:
+            raise ValueError(f"{name} must fit a signed 64-bit tick")
+        if a.ndim == 0:
+            a = np.full(T, int(a), np.int64)
+        if a.shape != (T,):
+            raise ValueError(f"{name}: expected {T} ticks or a scalar, got shape {tuple(a.shape)}")
+        out.append(np.ascontiguousarray(a.astype(np.int64)))
+    lo, hi = out
+    if T and (int(lo.min()) < 0 or int(hi.min()) < 0):
+        raise ValueError("open_tick and close_tick must not be negative")
+    if (lo > hi).any():
+        raise ValueError(f"task {int(np.argmax(lo > hi))} opens after it closes")
+    return lo, hi
+
+
 def _destroy_board(ctx, handle):
     """A task board's finalizer (set_task_board), as _destroy_field."""
     L = _lib._lib
@@ -1189,7 +1217,7 @@ class Swarm:
 
     # ------------------------------------------------------------------ task loop on boards of any size (U1-B)
     def set_task_board(self, tx, ty=None, treq=None, *, status_slots: int = 16, table_slots: int = 16,
-                       velocities=None):
+                       velocities=None, open_tick=None, close_tick=None):
         """set_tasks for a board of up to 2^24 tasks (contract U1-B; swarm_board_create): every task OPEN at
         every agent, every claim table empty, nothing in flight, the per-agent state sparse -- status_slots
         non-OPEN statuses and table_slots claim-table entries per agent at most, each in [1, 4096].  An agent
@@ -1198,7 +1226,9 @@ class Swarm:
         (SwarmError ERR_ARG).  The 64-task board of set_tasks is a separate one and is left alone.
         velocities ((T, 2), finite): a moving board (contract U1-M; swarm_board_create_moving) -- after every tick
         of update_loop_board each task advances by fl(v * dt), the cell grid is rebuilt on the device before every
-        tick, and a claim is heard with the positions it was sent with; board_positions() reads them back."""
+        tick, and a claim is heard with the positions it was sent with; board_positions() reads them back.
+        open_tick / close_tick ((T,) ints or scalars; either one makes the board a moving one, at rest unless
+        velocities are given): task lifetimes (contract U1-A; set_board_lifetimes)."""
         import weakref
         ids = None
         if ty is None and isinstance(tx, tuple) and len(tx) == 4:
@@ -1218,6 +1248,9 @@ class Swarm:
             if not 1 <= k <= _lib.BOARD_MAX_SLOTS:
                 raise ValueError(f"{name} must be in [1, {_lib.BOARD_MAX_SLOTS}], got {k}")
         vel = None if velocities is None else _board_velocities(velocities, T)
+        life = _board_lifetimes(open_tick, close_tick, T)
+        if life is not None and vel is None:
+            vel = np.zeros((T, 2))
         old = getattr(self, "board", None)
         if old is not None:
             old["finalizer"]()
@@ -1245,7 +1278,61 @@ class Swarm:
                           finalizer=weakref.finalize(self, _destroy_board, ctx, handle))
         self.board_task_ids = np.arange(T, dtype=np.int64) if ids is None else np.asarray(ids, np.int64)
         self.last_board_overflow = None
+        if life is not None:
+            self._set_lifetimes(*life)
         return self
+
+    def _set_lifetimes(self, lo, hi):
+        b = self.board
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().swarm_board_set_lifetimes(
+                b["ctx"], b["handle"], None if lo is None else lo.ctypes.data_as(ctypes.c_void_p),
+                None if hi is None else hi.ctypes.data_as(ctypes.c_void_p), _lib.stream()))
+        b["life"] = None if lo is None else (lo.copy(), hi.copy())
+
+    def set_board_lifetimes(self, open_tick, close_tick):
+        """Task lifetimes for the moving board of set_task_board (contract U1-A, DESIGN 4q;
+        swarm_board_set_lifetimes), allowed between calls: task k is present at tick t -- the absolute ticks
+        update_loop_board counts and loss= hashes -- iff open_tick[k] <= t < close_tick[k].  (T,) ints or scalars;
+        None for open_tick is tick 0, for close_tick never; both None removes the lifetimes.  Only present tasks are
+        offered; a conflict about an absent task writes nothing; at the tick a task closes, and at the first tick
+        after this call, the status entries of absent tasks leave every agent's row (their slots are free again),
+        while claim tables keep theirs.  ValueError: a negative tick, open > close, a wrong shape."""
+        if not hasattr(self, "board"):
+            raise RuntimeError("no task board: call set_task_board() first")
+        b = self.board
+        if not b.get("moving"):
+            raise RuntimeError("the task board does not move: lifetimes need set_task_board(..., velocities=...) "
+                               "or set_task_board(..., open_tick=..., close_tick=...)")
+        life = _board_lifetimes(open_tick, close_tick, b["T"])
+        self._set_lifetimes(*(life if life is not None else (None, None)))
+        return self
+
+    def board_lifetimes(self):
+        """(open_tick, close_tick), each a (T,) int64 numpy array read back from the board
+        (swarm_board_lifetimes); None when the board has no lifetimes."""
+        b = self.board
+        lo, hi = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(_lib.lib().swarm_board_lifetimes(b["handle"], ctypes.byref(lo), ctypes.byref(hi)))
+        if not lo.value:
+            return None
+        out = np.zeros(b["T"], np.int64), np.zeros(b["T"], np.int64)
+        if b["T"]:
+            with torch.cuda.device(self.device):
+                torch.cuda.current_stream().synchronize()
+                for a, p in zip(out, (lo, hi)):
+                    _lib.copy_to_host(a, p)
+        return out
+
+    def board_present(self, tick=None) -> np.ndarray:
+        """(T,) bool: the tasks present at `tick` (default: the next tick to run); all of them on a board without
+        lifetimes."""
+        b = self.board
+        life = b.get("life")
+        if life is None:
+            return np.ones(b["T"], bool)
+        t = getattr(self, "fsm_tick", 0) + 1 if tick is None else int(tick)
+        return (life[0] <= t) & (t < life[1])
 
     def update_loop_board(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
                           kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
@@ -1353,7 +1440,12 @@ class Swarm:
         task_ids = self.board_task_ids if task_ids is None else task_ids
         st = self.to_input_order(self.board_status())
         tt, tw, tu = (self.to_input_order(t) for t in self.board_tables())
+        # (contract U1-A) the tasks absent at the last tick run are no entry of an agent's `tasks`
+        gone = [int(task_ids[k]) for k in np.flatnonzero(~self.board_present(getattr(self, "fsm_tick", 0)))] \
+            if self.board.get("life") is not None else ()
         for i, a in enumerate(agents):
+            for key in gone:
+                a.tasks.pop(key, None)
             for e in st[i][st[i] >= 0]:
                 task = a.tasks.get(int(task_ids[int(e) >> 2]))
                 if task is not None:

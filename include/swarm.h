@@ -1083,6 +1083,36 @@ int swarm_update_loop_board_moving(swarm_ctx *ctx, int64_t n, const int32_t *ids
                                    swarm_board_overflow *overflow);
 
 /*
+ * Task lifetimes (contract U1-A): a board whose tasks open and close during a run.
+ * A moving board may carry one window of absolute ticks per task -- the ticks a lossy channel hashes --
+ * open_tick and close_tick (T i64 each).  Task k is present at tick t iff open[k] <= t < close[k]; INT64_MAX
+ * never closes; open == close is never present.  A board without lifetimes is the board as it was.
+ *   Handlers.   Before tick t every agent deletes tasks[k] for each k that stops being present and sets
+ *               tasks[k] = OPEN for each k that becomes present; then the tick runs U1-B (U1-L, U1-M) word for word.
+ *   Offering.   Only present tasks reach the claim evaluation and the guard-band count: an absent task is in no
+ *               cell's run of the tick's lists.
+ *   Conflicts.  A TASK_CONFLICT about a task absent at the receiving tick writes nothing.
+ *   Claims.     A TASK_CLAIM about a task absent at the hearing tick is arbitrated as ever: the table entry is
+ *               made and the conflict sent (nobody acts on it).  Table entries are never removed by a close.
+ *   Positions.  cur / lag advance for absent tasks too.
+ *   Retiring.   Tick t retires if some close[k] == t, or if it is the first tick of the first call after the
+ *               lifetimes were set or changed: at its start every status entry of an absent task leaves its row,
+ *               which is canonical again.  claim_out / conflict_out are message records and keep theirs.  A
+ *               tick's removals precede its inserts, so a row overflows iff its end-of-tick count exceeds Ks.
+ *   Refusals.   A refused call restores rows and positions as before; no call writes the lifetimes.  A run cut
+ *               into chunks is the single run bit for bit, and all windows (0, INT64_MAX) give the bits of the
+ *               board without lifetimes.
+ * swarm_board_set_lifetimes (waits for the stream): open_tick / close_tick are device or host arrays, copied;
+ * NULL / NULL removes the lifetimes.  SWARM_ERR_ARG, nothing changed: a NULL ctx or board, only one array, a board
+ * of another ctx or a dead one, a static board, a negative tick, open > close.
+ * swarm_board_lifetimes: the device pointers of the board's copies (NULL, NULL: none).
+ * swarm_update_loop_board_moving is the entry point; swarm_update_loop_board refuses the board as any moving one.
+ */
+int swarm_board_set_lifetimes(swarm_ctx *ctx, swarm_board *board, const int64_t *open_tick, const int64_t *close_tick,
+                              void *stream);
+int swarm_board_lifetimes(const swarm_board *board, const int64_t **open_tick, const int64_t **close_tick);
+
+/*
  * Restoring the spatial storage order of a moved swarm (contract R1).  No reference counterpart: the
  * reference keeps its agents in a Python list.  Three calls: the order (swarm_resort_plan), the per-agent arrays
  * moved into it (swarm_permute_rows), the neighbour graph renamed to it (swarm_graph_relabel).  Every value that
