@@ -182,7 +182,8 @@ def allocate_binned(ids, ax, ay, caps, tx, ty, treq, winner=None, util=None, cla
 def auction(ids, ax, ay, caps, tx, ty, treq, eps=0.1, claim_thr=20.0, u_scale=100.0, use_pow=False,
             max_rounds=1 << 20):
     """Jacobi auction over the admissible pairs (swarm_oracle.c orc_auction) -> dict(owner, price,
-    assigned, rounds, bidders, n_pairs).  use_pow=False: the GPU's x*x utility arithmetic."""
+    assigned, rounds, bidders, n_pairs).  use_pow=False: the GPU's x*x utility arithmetic.
+    Cut at max_rounds without converging: rounds == -1 and the state after max_rounds rounds."""
     ids = _c(ids, np.int32)
     n, t = len(ids), len(tx)
     owner = np.empty(t, np.int32)
@@ -195,8 +196,9 @@ def auction(ids, ax, ay, caps, tx, ty, treq, eps=0.1, claim_thr=20.0, u_scale=10
     r = lib().orc_auction(n, _p(ids), *[_p(a) for a in arrs], t, *[_p(a) for a in tarr], claim_thr,
                           u_scale, int(use_pow), float(eps), len(bidders), _p(owner), _p(price),
                           _p(assigned), _p(bidders), _p(npairs))
+    # rounds == -1: not converged, all max_rounds rounds ran (their bidder counts are returned)
     return dict(owner=owner, price=price, assigned=assigned, rounds=int(r),
-                bidders=bidders[: max(r, 0)].copy(), n_pairs=int(npairs[0]))
+                bidders=bidders[: r if r >= 0 else len(bidders)].copy(), n_pairs=int(npairs[0]))
 
 
 def physics(ids, state, leader, x, y, vx, vy, tx, ty, has_t, obs, row_ptr, col, dt=0.1, max_speed=5.0,
@@ -337,7 +339,7 @@ def allocate_py(ids, ax, ay, caps, tx, ty, treq, claim_thr=20.0, hysteresis=5.0)
     return np.array(winner, np.int32), np.array(util), np.array(nmsg)
 
 
-def auction_py(ids, ax, ay, caps, tx, ty, treq, eps=0.1, claim_thr=20.0, max_rounds=100000):
+def auction_py(ids, ax, ay, caps, tx, ty, treq, eps=0.1, claim_thr=20.0, max_rounds=100000, u_scale=100.0):
     """Straight restatement of the Jacobi auction (tiny inputs only): numpy float32 scalars
     carry the f32 arithmetic, the x*x utility as on the GPU."""
     n, t = len(ids), len(tx)
@@ -349,7 +351,7 @@ def auction_py(ids, ax, ay, caps, tx, ty, treq, eps=0.1, claim_thr=20.0, max_rou
             dx, dy = float(ax[a]) - float(tx[k]), float(ay[a]) - float(ty[k])
             d = math.sqrt(dx * dx + dy * dy)
             has = 0.0 if (int(treq[k]) >= 0 and not (int(caps[a]) >> int(treq[k])) & 1) else 1.0
-            U = (100.0 / (1.0 + d)) * has
+            U = (u_scale / (1.0 + d)) * has
             if U > claim_thr:
                 row.append((k, f(U)))
         cand.append(row)

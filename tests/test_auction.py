@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from auction_cases import _check_properties
 from swarm_amd import gen
 
 
@@ -21,32 +22,6 @@ def _inputs(n, seed, t=None):
         for k in ("tx", "ty", "treq"):
             d[k] = d[k][:0]
     return d
-
-
-def _check_properties(d, res, eps=0.1, thr=20.0):
-    """Matching consistency, prices, and eps-complementary slackness at termination."""
-    from oracle import oracle
-    owner, price, assigned = res["owner"], res["price"], res["assigned"]
-    n, t = len(d["ids"]), len(d["tx"])
-    for k in range(t):
-        if owner[k] >= 0:
-            assert assigned[owner[k]] == k
-    for a in range(n):
-        if assigned[a] >= 0:
-            assert owner[assigned[a]] == a
-    assert (price >= 0).all()
-    assert ((price > 0) == (owner >= 0)).all()  # a task's price rises exactly when it is taken
-    # eps-CS: an assigned agent's net value is within eps of its best alternative (incl. 0)
-    rng = np.random.default_rng(0)
-    for a in rng.choice(n, size=min(n, 50), replace=False):
-        if assigned[a] < 0:
-            continue
-        U = oracle.utility(np.full(t, d["x"][a]), np.full(t, d["y"][a]), np.full(t, d["caps"][a], np.uint32),
-                           d["tx"], d["ty"], d["treq"], use_pow=False)
-        adm = U > thr
-        net = np.where(adm, U.astype(np.float32) - price, -np.inf)
-        mine = np.float32(U[assigned[a]]) - price[assigned[a]]
-        assert mine >= max(net.max(), 0.0) - eps - 1e-4
 
 
 @pytest.mark.parametrize("n,seed", [(1, 11), (60, 1), (300, 2), (700, 3)])
