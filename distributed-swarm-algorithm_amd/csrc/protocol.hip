@@ -2609,6 +2609,10 @@ static int board_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos
     SW_ARG(board->moving == (mboard != nullptr),
            mboard ? "the board does not move (swarm_update_loop_board takes it)"
                   : "a moving board needs swarm_update_loop_board_moving (this loop would read it as a frozen board)");
+    // (contract U1-P.7) a board that has been placed on runs on from its own last tick: the new windows were
+    // checked against it
+    SW_ARG(!(mboard && mboard->placed_on && n > 0 && ticks > 0) || t0 == mboard->last_tick,
+           "tasks have been placed on this board: the call must start at the tick after the last one run on it");
     const LoopArgs loop{pos, pos_prev, vel, target, has_target, m, obstacles, nullptr, nullptr, max_speed,
                         trace, trace_every, n_singular, sense_radius, refused_tick, radio_radius};
     TickRun r{ctx, n, ids, pos, nullptr, nullptr, nullptr, nullptr, tick_off, fsm, t0, ticks, dt,
@@ -2620,7 +2624,11 @@ static int board_loop(swarm_ctx *ctx, int64_t n, const int32_t *ids, double *pos
     r.overflow = overflow;
     const int rc = run_loop(kLoopRadio, r);
     // (contract U1-A.7) the first tick of a call that ran has retired: a refused call keeps nothing, that too
-    if (rc == SWARM_OK && mboard && n > 0 && ticks > 0 && r.boarded()) mboard->life_fresh = false;
+    // (contract U1-P) ... and the board remembers the last tick run on it
+    if (rc == SWARM_OK && mboard && n > 0 && ticks > 0 && r.boarded()) {
+        mboard->life_fresh = false;
+        mboard->last_tick = t0 + ticks;
+    }
     return rc;
 }
 

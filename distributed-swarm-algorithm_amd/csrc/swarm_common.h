@@ -162,6 +162,15 @@ struct swarm_board {
     std::vector<int64_t> close_ticks;                     // the closing ticks, ascending, each once
     bool life_fresh = false;  // set or changed, and no call has run since: the next call's first tick retires
     bool alive() const { return life_open != nullptr; }
+    // Placing (contract U1-P; task_place.h): the last tick a loop ran on the board, the requests'
+    // staging buffer, the mask of the slots a place has just written (all zero between places) and the purge pass's
+    // per-wave counts.
+    int64_t last_tick = -1;       // -1: no loop call has run on this board
+    bool placed_on = false;       // a place has succeeded: the next call must start at last_tick + 1
+    void *place_buf = nullptr;    // device: one place's requests and the old windows of their slots
+    uint8_t *placed = nullptr;    // device: T
+    void *purge_part = nullptr;   // device: one count per wave of the purge pass
+    size_t cap_place = 0, cap_part = 0;
 };
 
 struct swarm_ctx {

@@ -11,6 +11,7 @@
 #include "task_grid.h"
 #include "task_life.h"
 #include "task_motion.h"
+#include "task_place.h"
 #include "utility.h"
 
 namespace swarm {
@@ -21,7 +22,7 @@ namespace {
 void release_board(swarm_board *b) {
     void *const dev[] = {b->tpos,    b->treq,    b->cell_off, b->sxy,     b->sir,     b->verdict, b->lag,    b->vel,
                          b->entry,   b->box,     b->keys[0],  b->keys[1], b->vals[0], b->vals[1], b->dyn_off, b->cub_tmp,
-                         b->life_open, b->life_close, b->present};
+                         b->life_open, b->life_close, b->present, b->place_buf, b->placed, b->purge_part};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (b->verdict_host) (void)hipHostFree(b->verdict_host);
@@ -262,6 +263,159 @@ __global__ __launch_bounds__(kBlock) void k_board_retire(const unsigned long lon
         }
         for (int q = kept + lig; q < seen; q += L) rp[q] = -1;
     }
+}
+
+// ---- placing (contract U1-P) ----
+//
+// One place's requests in the board's staging buffer, m of each: 16-byte sections first, so that every section is
+// aligned to its element.
+struct PlaceReq {
+    double2 *pos, *vel;
+    int64_t *open, *close, *old_open, *old_close;
+    int32_t *idx;
+    int8_t *req;
+};
+constexpr size_t kPlaceBytes = 16 + 16 + 8 + 8 + 8 + 8 + 4 + 1;  // per request
+
+PlaceReq place_sections(void *buf, size_t m) {
+    char *p = static_cast<char *>(buf);
+    PlaceReq r;
+    r.pos = reinterpret_cast<double2 *>(p), r.vel = reinterpret_cast<double2 *>(p + 16 * m);
+    r.open = reinterpret_cast<int64_t *>(p + 32 * m), r.close = reinterpret_cast<int64_t *>(p + 40 * m);
+    r.old_open = reinterpret_cast<int64_t *>(p + 48 * m), r.old_close = reinterpret_cast<int64_t *>(p + 56 * m);
+    r.idx = reinterpret_cast<int32_t *>(p + 64 * m), r.req = reinterpret_cast<int8_t *>(p + 68 * m);
+    return r;
+}
+
+// The current windows of the m listed slots, for the host's eligibility check: m entries, not T.  A request that
+// names no slot reads nothing (the host refuses it by its index alone).
+__global__ __launch_bounds__(kBlock) void k_board_place_fetch(int64_t m, int64_t T, PlaceReq r,
+                                                             const int64_t *__restrict__ open,
+                                                             const int64_t *__restrict__ close) {
+    for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < m; j += int64_t(gridDim.x) * kBlock) {
+        const int32_t k = r.idx[j];
+        const bool in = k >= 0 && k < T;
+        r.old_open[j] = in ? open[k] : 0;
+        r.old_close[j] = in ? close[k] : 0;
+    }
+}
+
+// The scatter of m checked requests (no slot twice): cur = lag = the new position, the requirement, the velocity,
+// the window; placed[k] = 1 for the purge pass (NULL: the tables are kept).
+__global__ __launch_bounds__(kBlock) void k_board_place(int64_t m, int64_t T, PlaceReq r, double2 *__restrict__ cur,
+                                                       double2 *__restrict__ lag, double2 *__restrict__ vel,
+                                                       int8_t *__restrict__ treq, int64_t *__restrict__ open,
+                                                       int64_t *__restrict__ close, uint8_t *__restrict__ placed) {
+    for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < m; j += int64_t(gridDim.x) * kBlock) {
+        const int32_t k = r.idx[j];
+        if (k < 0 || k >= T) continue;  // (refused on the host before this launch)
+        cur[k] = lag[k] = r.pos[j];
+        vel[k] = r.vel[j];
+        treq[k] = r.req[j];
+        open[k] = r.open[j];
+        close[k] = r.close[j];
+        if (placed) placed[k] = 1;
+    }
+}
+
+// The purge pass (contract U1-P.3): every claim-table entry about a placed slot leaves its row, the entries behind
+// it move down, the freed slots become (-1, -1, 0) -- a canonical row again.  k_board_retire's scheme over the
+// table's task words: 2^lg lanes per row, consecutive 4-byte loads, one ballot per 64 slots ranks the keepers, rows
+// of at most 64 slots kRetireTurn groups a turn with every load issued before the first ballot, longer rows in
+// chunks of 64 and left at the first chunk that is not full.  A row that loses nothing reads its task words only
+// and writes nothing; the winner and utility words are read, and moved with their task, only from the first chunk
+// that loses an entry on.  In place: a chunk's stores go to slots at or below the slots it has loaded.  An entry
+// outside [0, T) is kept (the loop's entry check owns that verdict).  part[wave]: the entries the wave removed.
+__global__ __launch_bounds__(kBlock) void k_board_purge(int64_t n, int32_t Kt, int32_t lg, int32_t T,
+                                                       const uint8_t *__restrict__ placed, int32_t *tab_task,
+                                                       int32_t *tab_winner, int32_t *tab_util,
+                                                       unsigned long long *__restrict__ part) {
+    const int L = 1 << lg, lane = threadIdx.x & (kWave - 1), sub = lane >> lg, lig = lane & (L - 1);
+    const int64_t per = kWave >> lg;  // rows per wave
+    const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> 6, nwaves = int64_t(gridDim.x) * (kBlock >> 6);
+    const uint64_t gm = lg == 6 ? ~0ull : ((1ull << L) - 1) << (sub * L);  // the lanes of this lane's row
+    const uint64_t below = gm & ((1ull << lane) - 1);
+    unsigned long long removed = 0;  // (counted by the first lane of each row)
+    if (Kt <= kWave) {
+        const int64_t step = nwaves * per;
+        for (int64_t r0 = wave * per; r0 < n; r0 += kRetireTurn * step) {  // (uniform over the wave)
+            int32_t e[kRetireTurn];
+            bool keep[kRetireTurn];
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) {
+                const int64_t row = r0 + u * step + sub;
+                e[u] = row < n && lig < Kt ? tab_task[row * Kt + lig] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) keep[u] = e[u] >= 0 && !(e[u] < T && placed[e[u]] != 0);
+            uint64_t mk[kRetireTurn], mv[kRetireTurn];
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) mk[u] = __ballot(keep[u]), mv[u] = __ballot(e[u] >= 0);
+#pragma unroll
+            for (int u = 0; u < kRetireTurn; ++u) {  // (no ballot below: the rows of a group part ways here)
+                if (mk[u] == mv[u]) continue;  // (uniform) no row of the group loses anything
+                const int at = __popcll(mk[u] & below), kept = __popcll(mk[u] & gm), seen = __popcll(mv[u] & gm);
+                if (kept != seen) {  // this lane's row loses an entry (seen > 0: the row exists)
+                    const int64_t base = (r0 + u * step + sub) * Kt;
+                    int32_t w = -1, f = 0;
+                    if (e[u] >= 0) w = tab_winner[base + lig], f = tab_util[base + lig];
+                    if (keep[u] && at != lig)
+                        tab_task[base + at] = e[u], tab_winner[base + at] = w, tab_util[base + at] = f;
+                    if (lig >= kept && lig < seen)
+                        tab_task[base + lig] = -1, tab_winner[base + lig] = -1, tab_util[base + lig] = 0;
+                    if (lig == 0) removed += unsigned(seen - kept);
+                }
+            }
+        }
+    } else {  // lg == 6: one row per wave
+        for (int64_t row = wave; row < n; row += nwaves) {  // (uniform over the wave)
+            const int64_t base = row * Kt;
+            int kept = 0, seen = 0;
+            for (int c = 0; c < Kt; c += kWave) {
+                const int idx = c + lane;
+                const int32_t e = idx < Kt ? tab_task[base + idx] : -1;
+                const bool valid = e >= 0;
+                const bool keep = valid && !(e < T && placed[e] != 0);
+                const uint64_t mk = __ballot(keep), mv = __ballot(valid);
+                const int at = kept + __popcll(mk & below);
+                kept += __popcll(mk);
+                const int nv = __popcll(mv);
+                seen += nv;
+                if (kept != seen) {  // (uniform) an entry has left at or before this chunk: the three words move
+                    int32_t w = -1, f = 0;
+                    if (valid) w = tab_winner[base + idx], f = tab_util[base + idx];
+                    if (keep && at != idx) tab_task[base + at] = e, tab_winner[base + at] = w, tab_util[base + at] = f;
+                }
+                if (nv < kWave) break;  // (uniform) the fillers are behind the entries
+            }
+            for (int q = kept + lane; q < seen; q += kWave) tab_task[base + q] = -1, tab_winner[base + q] = -1, tab_util[base + q] = 0;
+            if (lane == 0) removed += unsigned(seen - kept);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) removed += __shfl_xor(removed, off, 64);
+    if (lane == 0) part[wave] = removed;
+}
+
+// Behind the purge: the mask back to zero (m stores, not T) and the waves' counts summed into out[0] by the first
+// workgroup.
+__global__ __launch_bounds__(kBlock) void k_board_place_done(int64_t m, int64_t T, const int32_t *__restrict__ idx,
+                                                            uint8_t *__restrict__ placed, int64_t nparts,
+                                                            const unsigned long long *__restrict__ part,
+                                                            unsigned long long *__restrict__ out) {
+    for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < m; j += int64_t(gridDim.x) * kBlock) {
+        const int32_t k = idx[j];
+        if (k >= 0 && k < T) placed[k] = 0;
+    }
+    if (blockIdx.x != 0) return;
+    unsigned long long sum = 0;
+    for (int64_t q = threadIdx.x; q < nparts; q += kBlock) sum += part[q];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    __shared__ unsigned long long s[kBlock / kWave];
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = s[0] + s[1] + s[2] + s[3];
 }
 
 int sort_end_bit(int64_t ncells) {
@@ -624,6 +778,117 @@ int swarm_board_lifetimes(const swarm_board *board, const int64_t **open_tick, c
     SW_ARG(board != nullptr && open_tick != nullptr && close_tick != nullptr, "board, open_tick or close_tick is NULL");
     *open_tick = board->life_open;
     *close_tick = board->life_close;
+    return SWARM_OK;
+}
+
+int swarm_board_last_tick(const swarm_board *board, int64_t *last_tick) {
+    using namespace swarm;
+    SW_ARG(board != nullptr && last_tick != nullptr, "board or last_tick is NULL");
+    *last_tick = board->last_tick;
+    return SWARM_OK;
+}
+
+int swarm_board_place(swarm_ctx *ctx, swarm_board *board, int64_t n, const swarm_board_state *state, int64_t m,
+                      const int32_t *idx, const double *tpos, const int8_t *treq, const double *vel,
+                      const int64_t *open_tick, const int64_t *close_tick, uint32_t flags, int64_t *purged,
+                      void *stream) {
+    using namespace swarm;
+    SW_ARG(ctx != nullptr && board != nullptr && state != nullptr, "ctx, board or state is NULL");
+    SW_ARG((flags & ~uint32_t(SWARM_PLACE_KEEP_TABLES)) == 0, "unknown flag");
+    SW_ARG(n >= 0 && n < (int64_t(1) << 31), "n must be in [0, 2^31)");
+    SW_ARG(m >= 0, "m must not be negative");
+    SW_ARG(m == 0 || (idx && tpos && treq && open_tick && close_tick), "NULL request array");
+    SW_ARG(state->Ks >= 1 && state->Ks <= 4096 && state->Kt >= 1 && state->Kt <= 4096,
+           "status / table slots must be in [1, 4096]");
+    SW_ARG(live_board(ctx, board), "the board is not a live board of this ctx");
+    swarm_board *b = board;
+    SW_ARG(b->moving && b->alive(), "placing needs a moving board with lifetimes (swarm_board_set_lifetimes)");
+    SW_ARG(!b->life_fresh && b->last_tick >= 0,
+           "the lifetimes were set and no tick has run since: the retire they owe has not happened");
+    const bool purge = !(flags & SWARM_PLACE_KEEP_TABLES) && n > 0;
+    SW_ARG(!purge || (state->tab_task && state->tab_winner && state->tab_util), "NULL table array");
+    SW_ARG(m <= b->T, "more requests than slots: a slot is listed twice");
+    if (purged) *purged = 0;
+    if (m == 0) return SWARM_OK;
+    if (!ctx_on_current_device(ctx)) return SWARM_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t um = size_t(m);
+    const int64_t T = b->T, last = b->last_tick;
+    // the requests into the staging buffer (host or device arrays), the slots' current windows behind them
+    if (const int rc = grow(&b->place_buf, &b->cap_place, um * kPlaceBytes)) return rc;
+    const PlaceReq r = place_sections(b->place_buf, um);
+    SW_HIP(hipMemcpyAsync(r.idx, idx, um * 4, hipMemcpyDefault, s));
+    SW_HIP(hipMemcpyAsync(r.pos, tpos, um * 16, hipMemcpyDefault, s));
+    SW_HIP(hipMemcpyAsync(r.req, treq, um, hipMemcpyDefault, s));
+    SW_HIP(hipMemcpyAsync(r.open, open_tick, um * 8, hipMemcpyDefault, s));
+    SW_HIP(hipMemcpyAsync(r.close, close_tick, um * 8, hipMemcpyDefault, s));
+    if (vel)
+        SW_HIP(hipMemcpyAsync(r.vel, vel, um * 16, hipMemcpyDefault, s));
+    else
+        SW_HIP(hipMemsetAsync(r.vel, 0, um * 16, s));
+    hipLaunchKernelGGL(k_board_place_fetch, dim3(grid_for(m, kBlock, 4096)), dim3(kBlock), 0, s, m, T, r, b->life_open,
+                       b->life_close);
+    SW_LAUNCHED();
+    std::vector<char> host;
+    std::vector<int64_t> closes;
+    try {
+        host.resize(um * kPlaceBytes);
+        SW_HIP(hipMemcpyAsync(host.data(), b->place_buf, host.size(), hipMemcpyDeviceToHost, s));
+        SW_HIP(hipStreamSynchronize(s));  // the one wait before anything is written
+        const PlaceReq h = place_sections(host.data(), um);
+        int64_t bad = -1;
+        PlaceStatus st = place_check(T, last, m, h.idx, h.old_open, h.old_close, reinterpret_cast<double *>(h.pos),
+                                     reinterpret_cast<double *>(h.vel), h.req, h.open, h.close, &bad);
+        int32_t dup = -1;
+        if (st == kPlaceOk && place_has_duplicate(m, h.idx, &dup)) {
+            set_error("invalid argument: slot %d is listed twice", int(dup));
+            return SWARM_ERR_ARG;
+        }
+        if (st != kPlaceOk) {
+            set_error("invalid argument: request %lld (slot %d) %s", static_cast<long long>(bad), int(h.idx[bad]),
+                      place_reason(st));
+            return SWARM_ERR_ARG;
+        }
+        closes = b->close_ticks;
+        place_update_closes(&closes, last, m, h.close);
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory for %zu placed tasks", um);
+        return SWARM_ERR_OOM;
+    }
+    int64_t nparts = 0;
+    int lg = 0;
+    unsigned pgrid = 1;
+    if (purge) {  // the buffers first: an allocation that fails leaves the board as it was
+        while (lg < 6 && (1 << lg) < state->Kt) ++lg;
+        int64_t waves = (n + (kWave >> lg) - 1) / (kWave >> lg);
+        if (state->Kt <= kWave) waves = (waves + kRetireTurn - 1) / kRetireTurn;
+        pgrid = grid_for(waves * kWave, kBlock, 16384);
+        nparts = int64_t(pgrid) * (kBlock / kWave);
+        if (const int rc = grow(&b->purge_part, &b->cap_part, size_t(nparts) * 8)) return rc;
+        if (!b->placed) {
+            SW_HIP(hipMalloc(reinterpret_cast<void **>(&b->placed), size_t(T)));
+            SW_HIP(hipMemsetAsync(b->placed, 0, size_t(T), s));
+        }
+    }
+    hipLaunchKernelGGL(k_board_place, dim3(grid_for(m, kBlock, 4096)), dim3(kBlock), 0, s, m, T, r,
+                       reinterpret_cast<double2 *>(b->tpos), reinterpret_cast<double2 *>(b->lag),
+                       reinterpret_cast<double2 *>(b->vel), b->treq, b->life_open, b->life_close,
+                       purge ? b->placed : nullptr);
+    SW_LAUNCHED();
+    b->close_ticks.swap(closes);
+    b->placed_on = true;
+    if (purge) {
+        hipLaunchKernelGGL(k_board_purge, dim3(pgrid), dim3(kBlock), 0, s, n, state->Kt, lg, int32_t(T), b->placed,
+                           state->tab_task, state->tab_winner, reinterpret_cast<int32_t *>(state->tab_util),
+                           static_cast<unsigned long long *>(b->purge_part));
+        SW_LAUNCHED();
+        hipLaunchKernelGGL(k_board_place_done, dim3(grid_for(m, kBlock, 4096)), dim3(kBlock), 0, s, m, T, r.idx,
+                           b->placed, nparts, static_cast<const unsigned long long *>(b->purge_part), b->verdict + 5);
+        SW_LAUNCHED();
+        SW_HIP(hipMemcpyAsync(b->verdict_host + 5, b->verdict + 5, 8, hipMemcpyDeviceToHost, s));
+    }
+    SW_HIP(hipStreamSynchronize(s));  // the staging buffer and *purged end with this call
+    if (purge && purged) *purged = int64_t(b->verdict_host[5]);
     return SWARM_OK;
 }
 

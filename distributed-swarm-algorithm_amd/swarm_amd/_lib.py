@@ -47,7 +47,9 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_resort_plan", "swarm_board_create_moving", "swarm_board_set_velocities", "swarm_board_positions",
            "swarm_board_refresh", "swarm_board_call_box", "swarm_update_loop_board_moving",
            "swarm_graph_pairs_count", "swarm_graph_pairs_fill", "swarm_elect_pairs", "swarm_board_census",
-           "swarm_tasks_census", "swarm_board_set_lifetimes", "swarm_board_lifetimes")
+           "swarm_tasks_census", "swarm_board_set_lifetimes", "swarm_board_lifetimes", "swarm_board_place",
+           "swarm_board_last_tick")
+PLACE_KEEP_TABLES = 1  # swarm_board_place flags
 BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
 BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
 
@@ -273,6 +275,9 @@ def load(path: str = LIB_PATH):
         L.swarm_board_positions.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P)]
         L.swarm_board_set_lifetimes.argtypes = [P, P, P, P, P]
         L.swarm_board_lifetimes.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P)]
+        L.swarm_board_place.argtypes = [P, P, i64, ctypes.POINTER(BoardState), i64, P, P, P, P, P, P, ctypes.c_uint32,
+                                        ctypes.POINTER(i64), P]
+        L.swarm_board_last_tick.argtypes = [P, ctypes.POINTER(i64)]
         L.swarm_board_refresh.argtypes = [P, P, ctypes.POINTER(BoardDesc), P]
         L.swarm_board_call_box.argtypes = [P, P, d, i32, P, P]
         L.swarm_update_loop_board_moving.argtypes = L.swarm_update_loop_board.argtypes

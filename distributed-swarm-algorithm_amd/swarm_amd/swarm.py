@@ -1334,6 +1334,103 @@ class Swarm:
         t = getattr(self, "fsm_tick", 0) + 1 if tick is None else int(tick)
         return (life[0] <= t) & (t < life[1])
 
+    def _placeable_board(self):
+        if not hasattr(self, "board"):
+            raise RuntimeError("no task board: call set_task_board() first")
+        b = self.board
+        if not b.get("moving") or b.get("life") is None:
+            raise RuntimeError("placing needs a task board with lifetimes: set_task_board(..., open_tick=..., "
+                               "close_tick=...) or set_board_lifetimes()")
+        return b
+
+    def board_last_tick(self) -> int:
+        """The last tick update_loop_board ran on the board (swarm_board_last_tick); -1: none yet."""
+        t = ctypes.c_int64(-1)
+        _lib.check(_lib.lib().swarm_board_last_tick(self.board["handle"], ctypes.byref(t)))
+        return int(t.value)
+
+    def board_free_slots(self, tick=None) -> np.ndarray:
+        """The slots place_board_tasks may fill (contract U1-P.1, the quiet rule), ascending: those whose task was
+        absent at `tick` and at the tick before it -- tick: the last tick run (the default), since a place is
+        checked against that one."""
+        b = self._placeable_board()
+        last = getattr(self, "fsm_tick", 0) if tick is None else int(tick)
+        lo, hi = b["life"]
+        return np.flatnonzero((hi < last) | (lo > last) | (lo == hi))
+
+    def place_board_tasks(self, index, tx, ty, treq=None, *, velocities=None, open_tick=None, close_tick=None,
+                          keep_tables: bool = False, task_ids=None) -> dict:
+        """New tasks into the slots of closed ones (contract U1-P; swarm_board_place), between
+        update_loop_board calls: slot index[j] of the board takes position (tx[j], ty[j]), requirement treq[j]
+        (default none), velocity velocities[j] (default at rest) and the window [open_tick[j], close_tick[j]) --
+        open_tick defaults to the next tick to run, close_tick to never; scalars or one per slot.  Only a slot of
+        board_free_slots() can be placed.  Every claim-table entry about a placed slot is removed at every agent
+        unless keep_tables (the reference re-adding the same task id: the old winner's hysteresis then applies).
+        task_ids[j]: the dict key write_back_board gives the new task (default: unchanged).
+        -> {"purged": table entries removed, "next_tick": the tick the next update_loop_board call starts with}.
+        ValueError: shapes, ticks and values the library would refuse, found before the device is touched;
+        SwarmError ERR_ARG: what only the library sees, nothing changed."""
+        b = self._placeable_board()
+        T = b["T"]
+        idx = np.atleast_1d(np.asarray(index))
+        if idx.size == 0:
+            idx = idx.astype(np.int64)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu":
+            raise ValueError("index must be a 1-D array of integer slots")
+        idx = idx.astype(np.int64)
+        m = int(idx.shape[0])
+        if m and (int(idx.min()) < 0 or int(idx.max()) >= T):
+            raise ValueError(f"index: a slot outside [0, {T})")
+        if len(np.unique(idx)) != m:
+            raise ValueError("index: a slot is listed twice")
+        tx = np.atleast_1d(np.asarray(tx, np.float64))
+        ty = np.atleast_1d(np.asarray(ty, np.float64))
+        if tx.shape != (m,) or ty.shape != (m,):
+            raise ValueError(f"tx and ty: expected {m} values each")
+        if not (np.isfinite(tx).all() and np.isfinite(ty).all()):
+            raise ValueError("task positions must be finite")
+        tq = np.full(m, -1, np.int64) if treq is None else np.atleast_1d(np.asarray(treq)).astype(np.int64)
+        if tq.shape != (m,):
+            raise ValueError(f"treq: expected {m} values, got shape {tuple(tq.shape)}")
+        if m and (int(tq.min()) < -1 or int(tq.max()) > 31):
+            raise ValueError("treq must be in [-1, 31]")
+        vel = None if velocities is None else _board_velocities(velocities, m)
+        last = getattr(self, "fsm_tick", 0)
+        lo, hi = _board_lifetimes(last + 1 if open_tick is None else open_tick, close_tick, m)
+        if m and int(lo.min()) <= last:
+            raise ValueError(f"task {int(np.argmax(lo <= last))} opens at or before the last tick run ({last})")
+        ids = None
+        if task_ids is not None:
+            ids = np.atleast_1d(np.asarray(task_ids, np.int64))
+            if ids.shape != (m,):
+                raise ValueError(f"task_ids: expected {m} keys")
+        free = np.zeros(T, bool)
+        free[self.board_free_slots()] = True
+        if m and not free[idx].all():
+            raise ValueError(f"slot {int(idx[np.argmin(free[idx])])} is not free: its task was present at one of the "
+                             "last two ticks (board_free_slots() lists the free ones)")
+        purged = ctypes.c_int64(0)
+        if m:
+            i32 = np.ascontiguousarray(idx.astype(np.int32))
+            pos = np.ascontiguousarray(np.stack([tx, ty], 1))
+            rq = np.ascontiguousarray(tq.astype(np.int8))
+            p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            state = _lib.BoardState(b["Ks"], b["Kt"], None, _lib.ptr(b["status"]), _lib.ptr(b["tab_task"]),
+                                    _lib.ptr(b["tab_winner"]), _lib.ptr(b["tab_util"]), _lib.ptr(b["claim_out"]),
+                                    _lib.ptr(b["conflict_out"]))
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().swarm_board_place(
+                    b["ctx"], b["handle"], self.n, ctypes.byref(state), m, p(i32), p(pos), p(rq), p(vel), p(lo),
+                    p(hi), _lib.PLACE_KEEP_TABLES if keep_tables else 0, ctypes.byref(purged), _lib.stream()))
+            b["life"][0][idx], b["life"][1][idx] = lo, hi
+            if ids is not None:
+                old = self.board_task_ids[idx]
+                b.setdefault("left_ids", set()).update(int(k) for k in old[old != ids])
+                b["left_ids"].difference_update(int(k) for k in ids)
+                self.board_task_ids = self.board_task_ids.copy()
+                self.board_task_ids[idx] = ids
+        return {"purged": int(purged.value), "next_tick": last + 1}
+
     def update_loop_board(self, ticks: int, radio_radius: float, sense_radius: float, *, obstacles=None,
                           kill_ticks=(), dt: float = 0.1, timeout: float = 3.0, jitter: float = 0.2, seed: int = 0,
                           max_speed: float = 5.0, trace_every: int = 0, loss: float = 0.0,
@@ -1443,6 +1540,8 @@ class Swarm:
         # (contract U1-A) the tasks absent at the last tick run are no entry of an agent's `tasks`
         gone = [int(task_ids[k]) for k in np.flatnonzero(~self.board_present(getattr(self, "fsm_tick", 0)))] \
             if self.board.get("life") is not None else ()
+        # (contract U1-P) ... nor are the keys whose slot place_board_tasks gave to another task
+        gone = list(gone) + sorted(self.board.get("left_ids", ()))
         for i, a in enumerate(agents):
             for key in gone:
                 a.tasks.pop(key, None)

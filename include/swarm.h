@@ -1113,6 +1113,50 @@ int swarm_board_set_lifetimes(swarm_ctx *ctx, swarm_board *board, const int64_t 
 int swarm_board_lifetimes(const swarm_board *board, const int64_t **open_tick, const int64_t **close_tick);
 
 /*
+ * Placing tasks into the slots of closed ones (contract U1-P): a board of T slots serves an unbounded
+ * stream of tasks with at most T alive at once -- the reference's `tasks` dict taking a new key.  Between calls, on
+ * a moving board with lifetimes.  `last` is the last tick of the last successful swarm_update_loop_board_moving
+ * call on the board (swarm_board_last_tick; -1: none yet).
+ *   1 Eligibility (the quiet rule).  Slot k may be placed iff it was absent, under its current window, at ticks
+ *     last and last - 1: close[k] <= last - 1, or open[k] > last, or open[k] == close[k].  The last claim about k
+ *     was then heard at `close` at the latest and the conflict it caused at close + 1 <= last: no message in
+ *     flight names k, and claim_out / conflict_out need no purge.
+ *   2 Writes, per listed slot: cur[k] = lag[k] = the new position, treq[k], vel[k] (NULL: zero), open[k], close[k].
+ *     The new window needs open >= last + 1 and open <= close.
+ *   3 Purge.  Unless SWARM_PLACE_KEEP_TABLES is given, every claim-table entry about a placed slot leaves its row,
+ *     at every agent, dead ones included; tab_task / tab_winner / tab_util move together and the row stays
+ *     ascending with the empties (-1, -1, 0) last.  An entry outside [0, T) is kept.  With the flag the tables stay
+ *     -- the reference re-adding the same task id: the old winner's hysteresis applies to the new life.  Status
+ *     rows need nothing: the close retired them, and conflicts about an absent task write nothing.
+ *   4 Equivalence.  A run that places with purge equals, slot for slot, the U1-A run over a board with one index per
+ *     life: the statuses, tables and positions of the lives in slots, and every tick's counts.
+ *   5 Schedule.  The new close ticks join the board's retiring ticks; entries <= last are dropped.  Host work is
+ *     O(m log m + the number of closing ticks), never O(T).
+ *   6 Refusals, SWARM_ERR_ARG with nothing changed on host or device: a NULL ctx, board or state; an unknown flag;
+ *     n outside [0, 2^31); m < 0, or a NULL array (vel apart) with m > 0; state capacities outside [1, 4096]; a
+ *     NULL table array when the purge would read it; a board of another ctx or a dead one; a static board or one
+ *     without lifetimes; lifetimes set with no tick run since (the retire they owe has not happened); m > T; and,
+ *     after the call's one host wait, the first request that names a slot outside [0, T), a slot that is not
+ *     eligible, a negative tick, a window that opens at or before `last` or after it closes, a non-finite position
+ *     or velocity, a treq outside [-1, 31]; a slot listed twice.  m == 0 is SWARM_OK and touches nothing.
+ *   7 On a board that has been placed on, swarm_update_loop_board_moving refuses a call with n > 0 and ticks > 0
+ *     whose t0 is not `last` (SWARM_ERR_ARG, nothing written).  Boards never placed on behave as before.
+ *   8 A run cut into chunks with the same places between the same ticks is the same run bit for bit; a loop call
+ *     refused after a place restores rows and positions to what they were after the place.
+ * swarm_board_place: n agents' tables in `state` (only Ks, Kt and the three table arrays are read); m requests:
+ * idx (m i32), tpos (m x 2 f64), treq (m i8), vel (m x 2 f64 or NULL), open_tick / close_tick (m i64), each a
+ * device or a host array, copied.  The slots' current windows are fetched by a gather of m entries; after one host
+ * wait the scatter and the purge (one pass over n x Kt task words; a row that loses nothing is only read) are
+ * queued on the stream, and a second wait returns *purged (may be NULL), the number of table entries removed.
+ */
+#define SWARM_PLACE_KEEP_TABLES 1u
+int swarm_board_place(swarm_ctx *ctx, swarm_board *board, int64_t n, const swarm_board_state *state, int64_t m,
+                      const int32_t *idx, const double *tpos, const int8_t *treq, const double *vel,
+                      const int64_t *open_tick, const int64_t *close_tick, uint32_t flags, int64_t *purged,
+                      void *stream);
+int swarm_board_last_tick(const swarm_board *board, int64_t *last_tick);
+
+/*
  * Restoring the spatial storage order of a moved swarm (contract R1).  No reference counterpart: the
  * reference keeps its agents in a Python list.  Three calls: the order (swarm_resort_plan), the per-agent arrays
  * moved into it (swarm_permute_rows), the neighbour graph renamed to it (swarm_graph_relabel).  Every value that
