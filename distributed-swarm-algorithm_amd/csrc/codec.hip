@@ -43,7 +43,8 @@ __device__ __forceinline__ int enc_status(int64_t ty, int64_t snd, int64_t tick,
     const auto id_ok = [wide](int64_t v) { return wide ? u32_ok(v) : u8_ok(v); };  // (a function pointer here
     // compiled to an indirect call: SGPR spills and no inlining in the encode kernels)
     int st = 0, pl = 0;
-    switch (int(ty)) {
+    // the full 64-bit type: a value that is 1..5 only modulo 2^32 is an unknown type, whatever its low word says
+    switch (ty >= T_HB && ty <= T_CONFLICT ? int(ty) : 0) {
         case T_HB:  // payload '!ff' first
             if (!f32_ok(a) || !f32_ok(b)) st = 2;
             pl = 8;
@@ -66,7 +67,7 @@ __device__ __forceinline__ int enc_status(int64_t ty, int64_t snd, int64_t tick,
         default:
             st = 3;
     }
-    if (st == 0 && (!u8_ok(ty) || !id_ok(snd) || !u32_ok(tick))) st = 1;  // then the header
+    if (st == 0 && (!id_ok(snd) || !u32_ok(tick))) st = 1;  // then the header (a known type fits its byte)
     *len = st ? 0 : hdr + pl;
     return st;
 }
@@ -278,6 +279,11 @@ __global__ __launch_bounds__(1024) void k_enc_base(int64_t ntiles, const int32_t
     if (threadIdx.x == 1023) base[ntiles] = s_part[1023];
 }
 
+// U: `out` is not 16-byte aligned.  The head / 16-byte body / tail split is then made on the ADDRESS out + base
+// (po = out's own byte phase), so the 16-byte stores are aligned for any `out`; U = false is the aligned
+// form with po = 0 folded away (the host picks: swarm_codec_encode).  out == NULL (the sizing call) or a
+// total beyond cap: the offsets only, no byte is stored.
+template <bool U>
 __global__ __launch_bounds__(kEB) void k_enc_place(int64_t m, const uint8_t *__restrict__ tmp,
                                                      const int32_t *__restrict__ wave_tot,
                                                      const int64_t *__restrict__ base_of,
@@ -288,12 +294,17 @@ __global__ __launch_bounds__(kEB) void k_enc_place(int64_t m, const uint8_t *__r
     uint8_t *lb = reinterpret_cast<uint8_t *>(s_buf);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
     const int64_t ntiles = (m + kTile - 1) / kTile;
-    if (base_of[ntiles] > cap) {  // the caller's buffer is too small: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0) *err = 1u;
-        return;
-    }
+    const bool put = out && base_of[ntiles] <= cap;  // else the caller's buffer is too small: no byte is written
+    if (out && !put && blockIdx.x == 0 && threadIdx.x == 0) *err = 1u;
+    const int64_t po = U ? int64_t(reinterpret_cast<uintptr_t>(out) & 15) : 0;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t c0 = tile * kTile, base = base_of[tile];
+#pragma unroll 4
+        for (int j = 0; j < kTileJ; ++j) {
+            const int64_t i = c0 + j * kEB + threadIdx.x;
+            if (i < m) off[i] = base + loc[i];
+        }
+        if (!put) continue;
         int wo = 0, n = 0, mine = 0;
 #pragma unroll
         for (int q = 0; q < kWavesT; ++q) {
@@ -302,8 +313,10 @@ __global__ __launch_bounds__(kEB) void k_enc_place(int64_t m, const uint8_t *__r
             mine = q == w ? v : mine;
             n += v;
         }
-        // LDS byte ph + x holds out[base + x] (ph: the output's 16-byte phase); wave w stages its segment
-        const int ph = int(base & 15);
+        // positions counted from the 16-byte boundary at or below `out`: vb + x is byte out[base + x]; LDS byte
+        // ph + x holds it (ph: its 16-byte phase); wave w stages its segment
+        const int64_t vb = base + po;
+        const int ph = int(vb & 15);
         const uint4 *src = reinterpret_cast<const uint4 *>(tmp + tile * int64_t(kTileBytes) + w * kWaveBytes);
         for (int q = lane; q < (mine + 15) / 16; q += kWave) {
             const uint4 v4 = src[q];
@@ -313,20 +326,15 @@ __global__ __launch_bounds__(kEB) void k_enc_place(int64_t m, const uint8_t *__r
             for (int k = 0; k < 16; ++k)
                 if (k < lim) lb[ph + wo + 16 * q + k] = uint8_t(v[k >> 2] >> (8 * (k & 3)));
         }
-#pragma unroll 4
-        for (int j = 0; j < kTileJ; ++j) {
-            const int64_t i = c0 + j * kEB + threadIdx.x;
-            if (i < m) off[i] = base + loc[i];
-        }
         __syncthreads();
-        const int64_t end = base + n, abase = base - ph;
-        const int64_t A = (base + 15) & ~int64_t(15), B = end & ~int64_t(15);
+        const int64_t end = vb + n, abase = vb - ph;
+        const int64_t A = (vb + 15) & ~int64_t(15), B = end & ~int64_t(15);
         if (A >= B) {
-            for (int64_t x = base + threadIdx.x; x < end; x += kEB) out[x] = lb[x - abase];
+            for (int64_t x = vb + threadIdx.x; x < end; x += kEB) out[x - po] = lb[x - abase];
         } else {
-            if (threadIdx.x < A - base) out[base + threadIdx.x] = lb[base + threadIdx.x - abase];
-            if (threadIdx.x < end - B) out[B + threadIdx.x] = lb[B + threadIdx.x - abase];
-            uint4 *dst = reinterpret_cast<uint4 *>(out + A);
+            if (threadIdx.x < A - vb) out[base + threadIdx.x] = lb[vb + threadIdx.x - abase];
+            if (threadIdx.x < end - B) out[B - po + threadIdx.x] = lb[B + threadIdx.x - abase];
+            uint4 *dst = reinterpret_cast<uint4 *>(out + (A - po));
             const uint4 *sb = s_buf + (A - abase) / 16;
             for (int64_t q = threadIdx.x; q < (B - A) / 16; q += kEB) dst[q] = sb[q];
         }
@@ -373,7 +381,8 @@ __device__ __forceinline__ unsigned long long lb_word(uint32_t epoch, unsigned s
 #else
 #define SWARM_ENC_ATTR
 #endif
-template <int P>
+// U: `out` is not 16-byte aligned (a view into a larger buffer); the host picks (swarm_codec_encode).
+template <int P, bool U>
 __global__ __launch_bounds__(kEB) SWARM_ENC_ATTR void k_enc_one(int64_t m, EncIn in, int wide, int8_t *__restrict__ status,
                                                    int64_t *__restrict__ off, uint8_t *__restrict__ out, int64_t cap,
                                                    unsigned long long *__restrict__ lb, uint32_t epoch,
@@ -577,18 +586,20 @@ __global__ __launch_bounds__(kEB) SWARM_ENC_ATTR void k_enc_one(int64_t m, EncIn
     }
     if (!out || base + n > cap) return;  // sizing call, or a buffer too small (err set by the last tile)
     // out[base + x] = lbuf[x]: bytewise head and tail, 16-byte stores between, each composed from five
-    // LDS dwords shifted by the tile's byte phase
-    const int64_t end = base + n;
-    const int64_t A = (base + 15) & ~int64_t(15), B = end & ~int64_t(15);
+    // LDS dwords shifted by the tile's byte phase.  The split is made on the ADDRESS out + base: positions are
+    // counted from the 16-byte boundary at or below `out` (po = out's own byte phase; U = false: 0, folded away)
+    const int64_t po = U ? int64_t(reinterpret_cast<uintptr_t>(out) & 15) : 0;
+    const int64_t vb = base + po, end = vb + n;
+    const int64_t A = (vb + 15) & ~int64_t(15), B = end & ~int64_t(15);
     if (A >= B) {
-        for (int64_t x = base + threadIdx.x; x < end; x += kEB) out[x] = lbuf[x - base];
+        for (int64_t x = vb + threadIdx.x; x < end; x += kEB) out[x - po] = lbuf[x - vb];
         return;
     }
-    if (threadIdx.x < A - base) out[base + threadIdx.x] = lbuf[threadIdx.x];
-    if (threadIdx.x < end - B) out[B + threadIdx.x] = lbuf[B - base + threadIdx.x];
-    const int s0 = int(A - base), r = s0 & 3;
+    if (threadIdx.x < A - vb) out[base + threadIdx.x] = lbuf[threadIdx.x];
+    if (threadIdx.x < end - B) out[B - po + threadIdx.x] = lbuf[B - vb + threadIdx.x];
+    const int s0 = int(A - vb), r = s0 & 3;
     const uint32_t *ld = reinterpret_cast<const uint32_t *>(s_buf) + (s0 >> 2);
-    uint4 *dst = reinterpret_cast<uint4 *>(out + A);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + (A - po));
     for (int q = threadIdx.x; q < int(B - A) / 16; q += kEB) {
         const uint32_t *d = ld + 4 * q;
         const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
@@ -609,6 +620,14 @@ struct DecOut {
     uint8_t *has_pos;
 };
 
+// A float off the wire as the handlers see it: struct.unpack('!f') hands them a Python float (a double), and the
+// widening quiets a signalling NaN (payload kept), so that is the f32 reported.
+__device__ __forceinline__ float get_f32(const uint8_t *p) {
+    const uint32_t v = get_u32(p);
+    const bool nan = (v & 0x7FFFFFFFu) > 0x7F800000u;
+    return __uint_as_float(nan ? v | 0x00400000u : v);
+}
+
 // Parse one packet p[0, len) (the dispatch of on_message_received + the handlers' unpack).
 __device__ __forceinline__ void parse_packet(const uint8_t *p, int64_t len, bool inside, int wide, int64_t i,
                                              const DecOut &o) {
@@ -627,8 +646,8 @@ __device__ __forceinline__ void parse_packet(const uint8_t *p, int64_t len, bool
         switch (int(ty)) {
             case T_HB:
                 if (pl == 8) {
-                    a = __uint_as_float(get_u32(q));
-                    b = __uint_as_float(get_u32(q + 4));
+                    a = get_f32(q);
+                    b = get_f32(q + 4);
                     hp = 1;
                 }
                 break;
@@ -638,7 +657,7 @@ __device__ __forceinline__ void parse_packet(const uint8_t *p, int64_t len, bool
             case T_CLAIM:
                 if (pl == 8) {
                     task = int64_t(get_u32(q));
-                    a = __uint_as_float(get_u32(q + 4));
+                    a = get_f32(q + 4);
                 } else {
                     st = 3;
                 }
@@ -779,7 +798,9 @@ int swarm_codec_encode(swarm_ctx *ctx, int64_t m, const int64_t *type, const int
         const auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
         const bool pair = enc_pair() && al16(type) && al16(sender) && al16(tick) && al16(a) && al16(b) &&
                           al16(task) && al16(winner) && al16(offsets) && (reinterpret_cast<uintptr_t>(status) & 1) == 0;
-        hipLaunchKernelGGL(pair ? k_enc_one<2> : k_enc_one<1>, dim3(unsigned(ntiles)), dim3(kEB), 0, s, m, in,
+        const auto kern = al16(out) ? (pair ? k_enc_one<2, false> : k_enc_one<1, false>)
+                                    : (pair ? k_enc_one<2, true> : k_enc_one<1, true>);
+        hipLaunchKernelGGL(kern, dim3(unsigned(ntiles)), dim3(kEB), 0, s, m, in,
                            int(wide != 0), status, offsets, out, out ? cap : int64_t(0), lb, epoch, dev_tot, err,
                            fail);
         SW_LAUNCHED();
@@ -813,14 +834,11 @@ int swarm_codec_encode(swarm_ctx *ctx, int64_t m, const int64_t *type, const int
     SW_LAUNCHED();
     int64_t *host = static_cast<int64_t *>(pinned(ctx, 16));
     if (!host) return SWARM_ERR_OOM;
-    if (out == nullptr) {  // sizing call: the lengths only
-        SW_HIP(hipMemcpyAsync(host, base + ntiles, 8, hipMemcpyDeviceToHost, s));
-        SW_HIP(hipStreamSynchronize(s));
-        *total_bytes = host[0];
-        return SWARM_OK;
-    }
+    // (out == NULL, the sizing call: k_enc_place writes the offsets only)
     SW_HIP(hipMemsetAsync(err, 0, 4, s));
-    hipLaunchKernelGGL(k_enc_place, dim3(grid), dim3(kEB), 0, s, m, tmp, wt, base, loc, cap, offsets, out, err);
+    const bool al = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    hipLaunchKernelGGL(al ? k_enc_place<false> : k_enc_place<true>, dim3(grid), dim3(kEB), 0, s, m, tmp, wt, base, loc,
+                       cap, offsets, out, err);
     SW_LAUNCHED();
     SW_HIP(hipMemcpyAsync(host, base + ntiles, 8, hipMemcpyDeviceToHost, s));
     SW_HIP(hipMemcpyAsync(host + 1, err, 4, hipMemcpyDeviceToHost, s));

@@ -13,6 +13,9 @@ Message types (agent.py MsgType): 1 HEARTBEAT (a, b = leader x, y as '!ff'), 2 E
 struct.error (a field out of range, e.g. an ID > 255), 2 OverflowError (a finite value beyond
 f32), 3 unknown type; decode status 1 dropped (short packet), 2 unknown type, 3 the handler's
 unpack raises, 4 offsets outside the buffer (not read).  ``wide=True`` widens the u8 ID fields to u32 (IDs > 255; not in the reference).
+
+The library takes the output buffer of an encode and the ``buf`` of a decode at any alignment, so a view into a
+larger buffer (``big[3:]``) is as good as a fresh tensor; the other arrays need their natural alignment only.
 """
 from __future__ import annotations
 

@@ -543,8 +543,11 @@ int swarm_physics_run_sensed(swarm_ctx *ctx, int64_t n, const int32_t *ids, cons
  * value beyond f32), 3 unknown type -- payload checked before header, as the reference packs
  * them; an errored message takes no bytes.  offsets (device, m+1) = packet offsets into out,
  * offsets[m] = *total_bytes (host).  out == NULL: sizing call (status/offsets/total only);
- * otherwise cap must be >= the total (SWARM_ERR_RANGE: nothing past cap is written).  Synchronises
- * the stream (total_bytes).  One pass: tiles of 2 048 messages take their byte offsets from the lower
+ * otherwise cap must be >= the total (SWARM_ERR_RANGE: *total_bytes is the size needed, status and
+ * offsets are filled, nothing at or past out + cap is written).  out may have any alignment (a view
+ * into a larger buffer): the 16-byte stores are aligned on the address, not on the offset.  The
+ * field arrays, offsets and status need only their natural alignment.  Synchronises the stream
+ * (total_bytes).  One pass: tiles of 2 048 messages take their byte offsets from the lower
  * tiles' published counts (a ticket counter and look-back words in the ctx), so encode calls on one
  * ctx must not overlap (SWARM_ERR_HIP if they did and a look-back gave up).
  */
@@ -560,7 +563,9 @@ int swarm_codec_encode(swarm_ctx *ctx, int64_t m, const int64_t *type, const int
  * wide)), 4 offsets outside [0, buf_len] or decreasing (packet not read).  Fields not carried by
  * the type are 0; a HEARTBEAT carries a position (has_pos = 1,
  * a/b as f32) only when its payload is exactly 8 bytes (agent.py:256-258).  TASK_CLAIM
- * utility -> a.  Asynchronous on stream.
+ * utility -> a; a signalling NaN arrives quiet, payload kept, as the handlers' Python floats do.
+ * buf may have any alignment (a buffer that is not 16-byte aligned is parsed from global memory, not
+ * staged).  Asynchronous on stream.
  */
 int swarm_codec_decode(swarm_ctx *ctx, int64_t m, const uint8_t *buf, int64_t buf_len, const int64_t *offsets,
                        int32_t wide,
