@@ -147,8 +147,10 @@ int swarm_ctx_create(swarm_ctx **out) {
 
 int swarm_ctx_destroy(swarm_ctx *ctx) {
     if (!ctx) return SWARM_OK;
-    if (!ctx->fields.empty() || !ctx->boards.empty())
-        (void)hipDeviceSynchronize();  // a field or a board may still be read by queued work
+    if (!ctx->fields.empty() || !ctx->boards.empty() || !ctx->lives.empty())
+        (void)hipDeviceSynchronize();  // a field, a board or an event list may still be read by queued work
+    for (swarm_agent_life *h : ctx->lives) swarm::free_agent_life(h);
+    for (swarm_agent_life *h : ctx->life_graves) swarm::free_agent_life(h);
     for (swarm_obstacle_field *f : ctx->fields) swarm::free_obstacle_field(f);
     for (swarm_board *b : ctx->boards) swarm::free_board(b);
     for (swarm_board *b : ctx->board_graves) swarm::free_board(b);

@@ -121,4 +121,35 @@ int moving_field_restore_if_refused(swarm_obstacle_field *f, const unsigned long
 int moving_field_error(swarm_obstacle_field *f, unsigned long long *h_word, hipStream_t s);
 int moving_field_overflowed();
 
+// Agent lifetimes (contract U1-J; agent_life.hip).  What the event kernel writes: the run's records and
+// the caller's arrays, as run_ticks holds them.  A group of arrays the run does not have is NULL (vel: no loop;
+// sb: no task loop) or has a width of zero (T: the 64-task board; Ks / Kt: the sparse board).
+struct AgentEventArrays {
+    int64_t n;
+    uint2 *rec;
+    LRec *lrec;
+    double *last_hb, *wait_start, *delay;
+    int32_t *tick_off;
+    uint8_t *outbox;  // 2n, by tick parity
+    double2 *vel, *target;
+    uint8_t *has_target;
+    uint8_t *sb;  // 2n sender bytes of a task loop, by tick parity
+    int32_t T;
+    unsigned long long *status_lo, *status_hi, *claim_out, *conflict_out;  // claim / conflict: 2n
+    int32_t *tab_winner;
+    float *tab_util;
+    int32_t Ks, Kt;
+    int32_t *b_status, *b_tab_task, *b_tab_winner;
+    float *b_tab_util;
+    int32_t *b_claim_out, *b_conflict_out;  // 2n rows each
+    int64_t t0;
+    double dt;
+};
+// agent_life_begin  a call over the ticks t0+1 .. t0+ticks: its schedule (host only), and -- when it has events --
+//                   the handle's event list on the device (uploaded once per change of the windows, queued on s);
+// launch_agent_events  tick t's segment, one launch over its events alone (the caller asks sched.has_events first).
+int agent_life_begin(swarm_agent_life *h, int64_t t0, int32_t ticks, AgentSchedule *sched, hipStream_t s);
+int launch_agent_events(const swarm_agent_life *h, const AgentSchedule &sched, int64_t t, const AgentEventArrays &a,
+                        hipStream_t s);
+
 }  // namespace swarm

@@ -54,7 +54,8 @@
 // The host loop of every entry point is run_ticks, a sequence of stages that each own their scratch:
 // check_run_args, Counters (TickSums: a run's per-tick counters, also the task and link counts), pack_records,
 // PushState / RadioState / TaskState / launch_tick_pull (the receive launch by mode), EntrySnapshot (sensed),
-// TickClocks (A/B aid), tick_physics, read_back (one host wait).
+// TickClocks (A/B aid), tick_physics, read_back (one host wait).  Agent lifetimes (U1-J, agent_life.hip): a handle found
+// from fsm->alive; on a tick with events one launch over that tick's events, right after the leader kill.
 #include <cmath>
 #include <cstring>
 
@@ -2112,11 +2113,12 @@ struct EntrySnapshot {
     struct Kept {
         void *p;
         size_t bytes, at;
-    } kept[20];
+    } kept[24];
     int nkept = 0;
     uint8_t *snap = nullptr;
 
-    int take(const TickRun &r, hipStream_t s) {
+    // booted_tick_off: the tick offsets of a call with agent events (contract U1-J: a boot writes them), else NULL
+    int take(const TickRun &r, hipStream_t s, int32_t *booted_tick_off = nullptr) {
         const LoopArgs *loop = r.loop;
         const swarm_fsm *fsm = r.fsm;
         const size_t un = size_t(r.n);
@@ -2127,6 +2129,7 @@ struct EntrySnapshot {
                               {fsm->alive, un, 0},           {fsm->has_leader_pos, un, 0}};
         nkept = 0;
         for (int q = 0; q < 14; ++q) kept[nkept++] = all[q];
+        if (booted_tick_off) kept[nkept++] = Kept{booted_tick_off, un * 4, 0};
         if (r.tasked()) {  // U1-T: every task array as well
             const swarm_tasks &b = *r.tasks;
             const size_t row = un * size_t(b.T) * 4;
@@ -2323,6 +2326,13 @@ int run_ticks(const TickRun &r) {
     hipStream_t s = static_cast<hipStream_t>(r.stream);
     const LoopArgs *loop = r.loop;
     const bool sensed = r.sensed(), radio = r.radio(), push = r.push(), tasked = r.tasked(), boarded = r.boarded();
+    // (contract U1-J) agent lifetimes attached to this alive array: the call's events, found on the host
+    swarm_agent_life *life = find_agent_life(r.ctx, r.n, r.fsm->alive);
+    AgentSchedule events;
+    if (life) {
+        SW_ARG(r.tick_off == life->tick_off, "tick_off is not the array the agent lifetimes were created with");
+        if ((rc = agent_life_begin(life, r.t0, r.ticks, &events, s))) return rc;
+    }
     // U1-S / U1-R: the call's grid (the loop's one host wait before its end; non-finite positions are refused
     // here; U1-R: cells wide enough for the radio window too -- one binning per tick serves both halves)
     LoopSense ls{};
@@ -2341,7 +2351,7 @@ int run_ticks(const TickRun &r) {
         if (boarded && (rc = BoardState::entry_verdict(r))) return rc;
         if (boarded && r.mboard && (rc = moving_board_begin(r.mboard, s))) return rc;
         if (mov && (rc = moving_field_begin(mov, r.ticks, r.dt, true, s))) return rc;
-        if ((rc = snap.take(r, s))) return rc;
+        if ((rc = snap.take(r, s, events.empty() ? nullptr : life->tick_off))) return rc;
     }
     Counters cnt;
     if ((rc = cnt.lay(r, s))) return rc;
@@ -2362,6 +2372,48 @@ int run_ticks(const TickRun &r) {
     if (boarded && (rc = bs.begin(r, s))) return rc;
     const bool lossy = radio && r.lossy();
     if (lossy && (rc = links.begin(r, S_LINK_COUNTS, s))) return rc;
+    AgentEventArrays ev{};
+    if (!events.empty()) {
+        auto u64 = [](uint64_t *p) { return reinterpret_cast<unsigned long long *>(p); };
+        ev.n = r.n;
+        ev.rec = f.rec;
+        ev.lrec = f.lrec;
+        ev.last_hb = f.last_hb;
+        ev.wait_start = f.wait_start;
+        ev.delay = f.delay;
+        ev.tick_off = life->tick_off;
+        ev.outbox = r.fsm->outbox;
+        if (loop) {
+            ev.vel = reinterpret_cast<double2 *>(loop->vel);
+            ev.target = reinterpret_cast<double2 *>(loop->target);
+            ev.has_target = loop->has_target;
+        }
+        if (tasked) {
+            const swarm_tasks &b = *r.tasks;
+            ev.sb = ts.sb;
+            ev.T = b.T;
+            ev.status_lo = u64(b.status_lo);
+            ev.status_hi = u64(b.status_hi);
+            ev.claim_out = u64(b.claim_out);
+            ev.conflict_out = u64(b.conflict_out);
+            ev.tab_winner = b.tab_winner;
+            ev.tab_util = b.tab_util;
+        }
+        if (boarded) {
+            const swarm_board_state &q = *r.bstate;
+            ev.sb = bs.sb;
+            ev.Ks = q.Ks;
+            ev.Kt = q.Kt;
+            ev.b_status = q.status;
+            ev.b_tab_task = q.tab_task;
+            ev.b_tab_winner = q.tab_winner;
+            ev.b_tab_util = q.tab_util;
+            ev.b_claim_out = q.claim_out;
+            ev.b_conflict_out = q.conflict_out;
+        }
+        ev.t0 = r.t0;
+        ev.dt = r.dt;
+    }
     double *cur = loop ? loop->pos : nullptr, *lag = loop ? loop->pos_prev : nullptr;  // P_{t-1}, P_{t-2}
     for (int64_t t = r.t0 + 1; t <= r.t0 + r.ticks; ++t) {
         // (a heartbeat sent during tick t-1 carries its sender's position of then: the loops' lagged buffer)
@@ -2372,6 +2424,8 @@ int run_ticks(const TickRun &r) {
             hipLaunchKernelGGL(k_kill_leaders, dim3(grid), dim3(kBlock), 0, s, r.n, f.rec);
             SW_LAUNCHED();
         }
+        // (contract U1-J) a tick with agent events: its deaths, then its boots, over that tick's events alone
+        if (events.has_events(t - r.t0 - 1) && (rc = launch_agent_events(life, events, t, ev, s))) return rc;
         // bin the snapshot P_{t-1}, judge its window work, sort a copy of it by cell (the call's grid reaches
         // far beyond the agents: offsets by search)
         if (sensed && (rc = loop_sense_tick(r.ctx, r.n, cur, int32_t(t - r.t0 - 1), &ls, s, true))) return rc;

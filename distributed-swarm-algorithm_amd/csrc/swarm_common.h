@@ -12,6 +12,7 @@
 
 #include "../../include/swarm.h"
 #include "grid_shape.h"  // struct Grid (here so that headers without hipCUB can hold one) and its shaping
+#include "agent_life.h"  // AgentEvent, AgentSchedule (host-only arithmetic)
 
 namespace swarm {
 
@@ -173,9 +174,27 @@ struct swarm_board {
     size_t cap_place = 0, cap_part = 0;
 };
 
+// Agent lifetimes (contract U1-J; agent_life.h has the schedule, agent_life.hip the handle and the event
+// kernel).  The handle is found by the loops from the alive array they are given anyway; it owns the sorted event
+// list and its device copy, nothing else.
+struct swarm_agent_life {
+    int64_t n = 0;
+    uint8_t *alive = nullptr;     // device: the caller's alive flags (the key of find_agent_life)
+    int32_t *tick_off = nullptr;  // device: the caller's tick offsets, written at a boot
+    std::vector<int64_t> boot, death;     // the windows, by storage row
+    std::vector<swarm::AgentEvent> events;  // every event, sorted (agent_life_events)
+    std::vector<uint32_t> entries_host;   // the events' entries in that order, as uploaded
+    uint32_t *entries = nullptr;          // device: their copy (hipMalloc, grown on demand)
+    size_t cap_entries = 0;
+    bool uploaded = false;  // `entries` holds entries_host
+    bool dead = false;      // destroyed: the emptied struct rests on the ctx's life_graves for a while
+};
+
 struct swarm_ctx {
     std::vector<swarm_obstacle_field *> fields;  // the live obstacle fields created on this ctx
     std::vector<swarm_board *> boards;           // the live task boards created on this ctx
+    std::vector<swarm_agent_life *> lives;       // the live agent-lifetime handles created on this ctx
+    std::vector<swarm_agent_life *> life_graves;  // the handles destroyed last (emptied structs, as board_graves)
     // The boards destroyed last (their memory freed, the structs kept): a new board cannot take the address of a
     // handle that has just died, so a stale handle is told from a live board whatever the allocator does.
     std::vector<swarm_board *> board_graves;
@@ -262,6 +281,14 @@ inline bool live_board(const swarm_ctx *ctx, const swarm_board *b) {
         if (q == b) return true;
     return false;
 }
+// The live lifetime handle of ctx whose alive array `alive` is (with its n), or NULL (agent_life.hip frees them).
+inline swarm_agent_life *find_agent_life(const swarm_ctx *ctx, int64_t n, const uint8_t *alive) {
+    if (alive)
+        for (swarm_agent_life *h : ctx->lives)
+            if (!h->dead && h->alive == alive && h->n == n) return h;
+    return nullptr;
+}
+void free_agent_life(swarm_agent_life *h);
 // A moving board's call (contract U1-M; task_board.hip), in the order a loop uses them: the span-box reduction
 // queued before the call's entry wait (its four doubles land in verdict_host[1..4]); after the wait the call's
 // grid, the buffers and the entry snapshot (SWARM_ERR_ARG before anything is written: a box without a finite

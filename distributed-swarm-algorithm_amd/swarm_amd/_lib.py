@@ -48,7 +48,8 @@ EXPORTS = ("swarm_last_error", "swarm_version", "swarm_ctx_create", "swarm_ctx_d
            "swarm_board_refresh", "swarm_board_call_box", "swarm_update_loop_board_moving",
            "swarm_graph_pairs_count", "swarm_graph_pairs_fill", "swarm_elect_pairs", "swarm_board_census",
            "swarm_tasks_census", "swarm_board_set_lifetimes", "swarm_board_lifetimes", "swarm_board_place",
-           "swarm_board_last_tick")
+           "swarm_board_last_tick", "swarm_agent_life_create", "swarm_agent_life_set", "swarm_agent_life_events",
+           "swarm_agent_life_destroy")
 PLACE_KEEP_TABLES = 1  # swarm_board_place flags
 BOARD_FITS, BOARD_STATUS, BOARD_TABLE = 0, 1, 2  # swarm_board_overflow.kind
 BOARD_MAX_TASKS, BOARD_MAX_SLOTS = 1 << 24, 4096
@@ -288,6 +289,10 @@ def load(path: str = LIB_PATH):
         L.swarm_permute_rows.argtypes = [P, i64, P, i32, ctypes.POINTER(Rows), P]
         L.swarm_graph_relabel.argtypes = [P, i64, P, P, P, P, P, P]
         L.swarm_resort_plan.argtypes = [P, i64, P, P, d, P, P, ctypes.POINTER(i64), P]
+        L.swarm_agent_life_create.argtypes = [P, i64, P, P, P, P, ctypes.POINTER(P)]
+        L.swarm_agent_life_set.argtypes = [P, P, i64, P, P, i64, P]
+        L.swarm_agent_life_events.argtypes = [P, P, i64, i32, P]
+        L.swarm_agent_life_destroy.argtypes = [P, P]
         for name in EXPORTS:
             if name not in ("swarm_last_error", "swarm_version"):
                 getattr(L, name).restype = ctypes.c_int

@@ -194,6 +194,43 @@ def _board_lifetimes(open_tick, close_tick, T):
     return lo, hi
 
 
+AGENT_BOOT_MAX = 1 << 31
+
+
+def _agent_lifetimes(boot_tick, death_tick, n):
+    """set_agent_lifetimes: the (n,) int64 windows of boot_tick / death_tick, each (n,) ints or a scalar; None for
+    boot_tick is tick 0, for death_tick never (contract U1-J).  (None, None): no lifetimes."""
+    if boot_tick is None and death_tick is None:
+        return None
+    out = []
+    for name, v, default in (("boot_tick", boot_tick, 0), ("death_tick", death_tick, LIFE_FOREVER)):
+        a = np.asarray(default if v is None else v)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be integer ticks, got dtype {a.dtype}")
+        if a.dtype.kind == "u" and a.size and int(a.max()) > LIFE_FOREVER:
+            raise ValueError(f"{name} must fit a signed 64-bit tick")
+        if a.ndim == 0:
+            a = np.full(n, int(a), np.int64)
+        if a.shape != (n,):
+            raise ValueError(f"{name}: expected {n} ticks or a scalar, got shape {tuple(a.shape)}")
+        out.append(np.ascontiguousarray(a.astype(np.int64)))
+    boot, death = out
+    if n and (int(boot.min()) < 0 or int(boot.max()) >= AGENT_BOOT_MAX):
+        raise ValueError("boot_tick must be in [0, 2^31)")
+    if n and int(death.min()) < 0:
+        raise ValueError("death_tick must not be negative")
+    return boot, death
+
+
+def _destroy_agent_life(ctx, handle):
+    """The finalizer of a swarm's agent lifetimes (set_agent_lifetimes), as _destroy_field."""
+    L = _lib._lib
+    if L is not None and handle.value and ctx.handle.value:
+        with torch.cuda.device(ctx.device):
+            L.swarm_agent_life_destroy(ctx.handle, handle)
+    handle.value = None
+
+
 def _destroy_board(ctx, handle):
     """A task board's finalizer (set_task_board), as _destroy_field."""
     L = _lib._lib
@@ -940,6 +977,7 @@ class Swarm:
         order, default 0.0 = the clock at tick 0); tick_off: each agent's tick-counter phase
         (input order, default 0 = lock-step).  Tick counter restarts at 0."""
         n, dev = self.n, self.device
+        self._drop_agent_life()
         z = lambda dt: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
         self.state.fill_(_lib.FOLLOWER)
         self.leader.fill_(-1)
@@ -980,6 +1018,8 @@ class Swarm:
             (_lib.ptr(h[0], torch.int32), _lib.ptr(h[1], torch.int32) if h[1].numel() else None)
         counts = np.zeros((int(ticks), 4), np.int64)
         tr = np.zeros(8, np.int64)
+        self._agent_life_current()
+        agent_events = self._agent_events(ticks)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().swarm_protocol_run_ex(
                 _lib.ctx(), self.n, _lib.ptr(self.ids) if self.n else None, _lib.ptr(self.pos) if self.n else None,
@@ -992,7 +1032,98 @@ class Swarm:
         if traffic:
             self.fsm_traffic = tr
         self.fsm_tick += int(ticks)
+        self.last_agent_events = agent_events
         return counts
+
+    # ------------------------------------------------------------------ agent lifetimes (U1-J)
+    def _drop_agent_life(self):
+        life = self.__dict__.pop("agent_life", None)
+        if life is not None:
+            life["finalizer"]()
+
+    def _attach_agent_life(self, boot, death, apply_rule):
+        """The handle of the windows (input order) on the current alive / tick_off tensors, in storage order;
+        apply_rule: the set-time rule at self.fsm_tick (swarm_agent_life_set)."""
+        import weakref
+        n = self.n
+        order = slice(None) if self.layout == "input" else self.perm.cpu().numpy().astype(np.int64)
+        bs, ds = np.ascontiguousarray(boot[order]), np.ascontiguousarray(death[order])
+        hp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if n else None  # noqa: E731
+        alive, tick_off = self.fsm["alive"], self.tick_off
+        old = getattr(self, "agent_life", None)
+        if apply_rule and old is not None and old["alive"] is alive and old["tick_off"] is tick_off:
+            # the handle stands on the current tensors: new windows and the set-time rule in one call
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().swarm_agent_life_set(old["ctx"], old["handle"], n, hp(bs), hp(ds),
+                                                           int(self.fsm_tick), _lib.stream()))
+            old["boot"], old["death"] = boot.copy(), death.copy()
+            return
+        self._drop_agent_life()
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            ctx = _lib.ctx()
+            _lib.check(_lib.lib().swarm_agent_life_create(ctx, n, hp(bs), hp(ds), _lib.ptr(alive) if n else None,
+                                                          _lib.ptr(tick_off) if n else None, ctypes.byref(handle)))
+            self.agent_life = dict(boot=boot.copy(), death=death.copy(), handle=handle, ctx=ctx, alive=alive,
+                                   tick_off=tick_off,
+                                   finalizer=weakref.finalize(self, _destroy_agent_life, ctx, handle))
+            if apply_rule:
+                _lib.check(_lib.lib().swarm_agent_life_set(ctx, handle, n, hp(bs), hp(ds), int(self.fsm_tick),
+                                                           _lib.stream()))
+
+    def _agent_life_current(self):
+        """The lifetimes' handle names the alive / tick_off tensors the next call passes: rebuilt on the current
+        ones when either has been replaced (resort() replaces both, with the storage order)."""
+        life = getattr(self, "agent_life", None)
+        if life is not None and (life["alive"] is not self.fsm["alive"] or life["tick_off"] is not self.tick_off):
+            self._attach_agent_life(life["boot"], life["death"], apply_rule=False)
+
+    def _agent_events(self, ticks) -> np.ndarray:
+        """(ticks x 2) the agents that boot and die at each of the next `ticks` ticks (swarm_agent_life_events)."""
+        ev = np.zeros((int(ticks), 2), np.int64)
+        life = getattr(self, "agent_life", None)
+        if life is not None and ticks:
+            _lib.check(_lib.lib().swarm_agent_life_events(life["ctx"], life["handle"], int(self.fsm_tick), int(ticks),
+                                                          ev.ctypes.data_as(ctypes.c_void_p)))
+        return ev
+
+    def set_agent_lifetimes(self, boot_tick, death_tick):
+        """Agent lifetimes (contract U1-J; swarm_agent_life_create / _set), allowed between calls: agent i
+        (input order) is up at tick t -- the absolute ticks the loops count -- iff boot_tick[i] <= t <
+        death_tick[i].  (n,) ints or scalars; None for boot_tick is tick 0, for death_tick never; both None removes
+        the lifetimes.  With self.fsm_tick = T the last tick run, agents with boot > T or death <= T lose their alive
+        flag now; the others keep the flag they have.  At the start of tick t of protocol_run and of every
+        update_loop*, after the leader kill of kill_ticks: agents with death == t die as a kill_ticks victim does
+        (alive = 0, everything else stays, what they sent during t-1 is still heard); then agents with boot == t
+        become a fresh SwarmAgent constructed at the clock of tick t-1 -- FOLLOWER, no leader, last_hb = (t-1) dt,
+        their own tick counter 1 at tick t, velocity 0, no target, nothing in flight, on a task board every task
+        OPEN again and an empty claim table -- at the position they stand at.  A boot of an agent that is up is a
+        restart; a second window set after a death is a rebirth.  A run cut into calls is the single run; a refused
+        call fires nothing.  The loops' dicts carry "agent_events" (ticks x 2: booted, died per tick);
+        protocol_run leaves it in self.last_agent_events.  protocol_reset() drops the lifetimes.  ValueError: a boot
+        tick outside [0, 2^31), a negative death tick, a wrong shape."""
+        life = _agent_lifetimes(boot_tick, death_tick, self.n)
+        if life is None:
+            self._drop_agent_life()
+            return self
+        if not hasattr(self, "fsm"):
+            self.protocol_reset()
+        self._attach_agent_life(*life, apply_rule=True)
+        return self
+
+    def agent_lifetimes(self):
+        """(boot_tick, death_tick), each a (n,) int64 numpy array in input order; None without lifetimes."""
+        life = getattr(self, "agent_life", None)
+        return None if life is None else (life["boot"].copy(), life["death"].copy())
+
+    def agents_up(self, tick=None) -> np.ndarray:
+        """(n,) bool, input order: the agents whose window holds `tick` (default: the next tick to run); all of
+        them without lifetimes.  (An agent killed at a kill tick is in its window and dead: fsm["alive"].)"""
+        life = getattr(self, "agent_life", None)
+        if life is None:
+            return np.ones(self.n, bool)
+        t = getattr(self, "fsm_tick", 0) + 1 if tick is None else int(tick)
+        return (life["boot"] <= t) & (t < life["death"])
 
     # ------------------------------------------------------------------ coupled update loop (U1)
     def _motion_state(self):
@@ -1659,6 +1790,8 @@ class Swarm:
         fs = _lib.Fsm(*[_lib.ptr(t) if n else None for t in
                         (self.state, self.leader, f["last_hb"], f["wait_start"], f["delay"], f["leader_pos"],
                          f["has_leader_pos"], f["alive"], f["outbox"])])
+        self._agent_life_current()
+        agent_events = self._agent_events(ticks)
         kt = np.ascontiguousarray(np.asarray(kill_ticks, np.int64))
         if radio_radius is None:
             h = getattr(self, "_hear", None) or (self.row_ptr, self.col)
@@ -1742,7 +1875,7 @@ class Swarm:
         self._pos_prev_key = (self.pos, self.pos._version)
         _lib.check(rc)
         self.fsm_tick += ticks
-        out = {"counts": counts, "singular": sing.value}
+        out = {"counts": counts, "singular": sing.value, "agent_events": agent_events}
         if trace_every:
             out["trace"] = trace
         if tasks is not None or board is not None:

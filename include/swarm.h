@@ -1271,6 +1271,59 @@ int swarm_tasks_census(swarm_ctx *ctx, int64_t n, const int32_t *ids, int32_t T,
                        const uint8_t *mask, const swarm_census *out, int32_t *holders, int64_t cap,
                        int64_t *n_holders, void *stream);
 
+/*
+ * Agent lifetimes (contract U1-J): agents that boot and die during a run.  The reference runs one
+ * process per agent (agent.py:349-358); a process that starts late is a fresh SwarmAgent.__init__ (agent.py:25-54),
+ * one that stops simply stops, one that restarts is both.
+ *
+ * Agent i (storage index) carries one window of absolute ticks and is up at tick t iff boot[i] <= t < death[i].
+ * The defaults boot = 0 and death = INT64_MAX mean "as it is, forever": with them every loop gives the bits it
+ * gives without a handle.  An agent with boot >= death is never up and has no events.
+ *
+ * swarm_agent_life_create attaches the windows (host arrays, n each, copied) to the swarm whose alive flags
+ * (device, n bytes: the array every loop is given as fsm->alive) and tick offsets (device, n int32: the loops'
+ * tick_off) are named; it touches no device memory.  Every protocol run and update loop of this ctx that is given
+ * this alive array then runs the events below; it must be given this tick_off as well (SWARM_ERR_ARG otherwise).
+ * One handle per alive array.  The two device arrays must outlive the handle.
+ *
+ * swarm_agent_life_set replaces the windows and applies the set-time rule, with last_tick the last tick run:
+ * agents with boot > last_tick or death <= last_tick get alive = 0, all others keep the flag they have (an agent
+ * killed at a kill tick stays dead), nothing else is written.  It waits for the stream.  A second window for an
+ * agent that has died gives a rebirth.
+ *
+ * At the start of tick t of a call, after the leader kill of a kill tick: first the deaths, then the boots.
+ *   death (death[i] == t)  alive = 0 and nothing else, exactly what a kill-tick victim is: what it sent during
+ *          t - 1 is still heard at t, its position stays and stays a separation neighbour.
+ *   boot  (boot[i] == t)   a fresh SwarmAgent constructed at the clock of tick t - 1: alive, FOLLOWER, leader -1,
+ *          no leader position, last_hb = (t - 1) dt, wait_start = delay = 0, its own tick counter 1 at tick t
+ *          (tick_off[i] = 1 - t), velocity 0, no target, both outbox halves empty; in the task loops an empty
+ *          status row (every task OPEN to it again), an empty claim table and no claim or conflict in flight, the
+ *          sparse rows in the empty encoding (-1 slots, utilities +0.0f).  Position, ID and capabilities stay.  It
+ *          receives at tick t what the up agents in range sent during t - 1.  A boot of an agent that is up is a
+ *          restart.
+ *          (swarm_protocol_run / _ex are not given velocity, target and has_target and leave them alone.)
+ * Every absolute tick runs once, so a run cut into calls is the single run bit for bit.  A refused call (a tick too
+ * dense to sense, a board overflow) writes nothing, tick_off included, and the repeated call fires the same events.
+ * A tick without events launches nothing; on a tick with events one kernel runs over that tick's events alone.
+ *
+ * swarm_agent_life_events: events (host, ticks x 2) = per tick of the call t0 + 1 .. t0 + ticks the agents that
+ * boot and the agents that die, from the schedule alone (host only).
+ * swarm_agent_life_destroy: the handle is dead (NULL: nothing happens); the loops run as without it.  Handles
+ * still alive are freed with their ctx.
+ *
+ * SWARM_ERR_ARG before anything is written, without a device: a NULL ctx, out, handle or array (the arrays may be
+ * NULL when n == 0); n outside [0, 2^31), or not the handle's; a handle that is dead or no handle of ctx; a boot
+ * tick outside [0, 2^31); a negative death tick or last_tick; an alive array that already has a handle.
+ */
+typedef struct swarm_agent_life swarm_agent_life;
+
+int swarm_agent_life_create(swarm_ctx *ctx, int64_t n, const int64_t *boot, const int64_t *death, uint8_t *alive,
+                            int32_t *tick_off, swarm_agent_life **out);
+int swarm_agent_life_set(swarm_ctx *ctx, swarm_agent_life *life, int64_t n, const int64_t *boot, const int64_t *death,
+                         int64_t last_tick, void *stream);
+int swarm_agent_life_events(swarm_ctx *ctx, const swarm_agent_life *life, int64_t t0, int32_t ticks, int64_t *events);
+int swarm_agent_life_destroy(swarm_ctx *ctx, swarm_agent_life *life);
+
 #ifdef __cplusplus
 }
 #endif
